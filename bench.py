@@ -18,9 +18,13 @@ be answered with a one-GPU line.  A world size that differs from --gpus is an er
 by points over the ranks, per-window partial sums exchanged with an RCCL
 all-gather and combined on every rank (strong scaling: the total work is fixed).
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed
-inside libzkmi on its launch stream) and, at N = 1, `cpu_baseline` (the in-repo
-C++ oracle prover on the host cores, bounded sample).
+A plain run of the proofs workload sets up, warms up, times the K steps and prints
+ONE JSON line (rank 0) with the headline figure.  `--full` adds everything else the line used to carry:
+the pairing check of the timed proofs, `roofline` (dominant kernel, HIP-event timed
+inside libzkmi on its launch stream), the secondary measurements and, at N = 1, the
+other BASELINE configs and `cpu_baseline` (the in-repo C++ oracle prover on the host
+cores, bounded sample).  `--dump-outputs DIR` writes what the timed path returned in
+its last step as DIR/<name>.npy (float64), for comparing two builds output for output.
 """
 import argparse
 import hashlib
@@ -607,6 +611,9 @@ def run_msm26(args, pkg, z, ctx, rank, world, use_dist):
     ctx.prof_reset()
     got, elapsed = timed_region(ctx, use_dist, lambda: [one() for _ in range(args.steps)][-1])
     ctx.prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        # the G1 point of the last step's MSM (wire format)
+        dump_outputs(args.dump_outputs, {"msm_g1": got})
     G = z.g1_generator()
     Q = z.g1_mul(G, (0xC0FFEE).to_bytes(32, "little"))
     want = z.g1_add(z.g1_mul(G, (tot % R_MOD).to_bytes(32, "little")), z.g1_mul(Q, (wtot % R_MOD).to_bytes(32, "little")))
@@ -670,6 +677,16 @@ def run_msm26(args, pkg, z, ctx, rank, world, use_dist):
     return out, 0 if ok else 1
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: each byte string of `arrays` as DIR/<name>.npy, one float64 per byte (exact), written after the
+    timed steps from what they returned."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, data in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.frombuffer(bytes(data), dtype=np.uint8).astype(np.float64))
+
+
 def mark_dry_run(out, world):
     """--shared-gpu-dry-run: the line must not be mistaken for a scaling point -- all ranks shared ONE GPU."""
     out["dry_run_shared_gpu"] = True
@@ -693,8 +710,15 @@ def main():
                     help="msm26: how the MSM is cut over the ranks -- by POINTS (SURVEY.md 8e's preferred partition, 1/N of the scalars and "
                          "bases per rank; default) or by WINDOWS (BASELINE configs[3] as worded: every rank holds all points)")
     ap.add_argument("--cpu-sample-log-n", type=int, default=20)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the H2D-inclusive and whole-MSM measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="proofs workload: besides the headline, the pairing check of the timed proofs, roofline / phase figures, "
+                         "the secondary measurements, the other BASELINE configs and the CPU baseline (off: set up, warm up, time, "
+                         "report).  --workload msm26 is a measurement of its own and always carries its closed-form check and roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float64): the last proof's 192 bytes (proofs) / the MSM result point (msm26)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the H2D-inclusive and whole-MSM measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--relation", choices=["poseidon", "chain"], default="poseidon")
     ap.add_argument("--pmc-summary", default="profiles/r06/pmc_summary_bench_steps3.json")
     ap.add_argument("--msm-pmc-summary", default="profiles/r06/pmc_summary_msm26_steps1.json")
@@ -799,11 +823,58 @@ def main():
     if args.warmup:
         run(0, args.warmup)
 
-    ctx.prof_enable(True)
-    ctx.prof_reset()
+    if args.full:
+        ctx.prof_enable(True)
+        ctx.prof_reset()
     proofs, elapsed = timed_region(ctx, use_dist, lambda: run(args.warmup, args.steps))
     proof = proofs[-1] if proofs else None
-    ctx.prof_enable(False)
+    if args.full:
+        ctx.prof_enable(False)
+    if args.dump_outputs and rank == 0 and proof is not None:
+        # the 192 proof bytes (A | B | C, compressed) of the last timed step
+        dump_outputs(args.dump_outputs, {"proof": proof})
+
+    out = {
+        "metric": "shielder_withdraw_groth16_proofs_per_sec_2^%d_constraints" % log_n,
+        "value": world * args.steps / elapsed,
+        "unit": "proofs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int: signed 28-bit limbs in 32-bit words, 64-bit column accumulators (Fr 255-bit / Fq 381-bit Montgomery)",
+        "data": "synthetic",
+        "config": {
+            "workload": "single withdraw-shaped Groth16 proof, N=2^%d (7 Fr NTTs, 4 G1 MSM + 1 G2 MSM of 2^%d-1 terms), 1 proof per step per GPU"
+            % (log_n, log_n),
+            "relation": "update_note (withdraw) with Poseidon-5 hashing, chain-padded to N" if args.relation == "poseidon"
+            else "hash-free chain stand-in",
+            "curve": "BLS12-381",
+            "independent_proofs_per_rank": args.steps,
+            "distinct_witnesses_per_rank": min(args.steps, n_distinct),
+            "fresh_r_s_per_proof": True,
+            "proofs_in_flight_per_gpu": 3,
+            # nothing is skipped: all five MSMs run in full; what is shared is the REDUCTION of the three queries that only
+            # ever appear summed in C (DESIGN.md 4.1) -- the proof bytes equal the oracle's prover's
+            "msm_schedule": "A | B1 (over r*z) + L + H reduced together | B2 (G2)",
+        },
+        "setup_seconds": setup_s,
+        "proofs_in_flight": 3,
+    }
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if dry:
+            mark_dry_run(out, world)
+        if rank == 0:
+            emit(out)
+        pk.free()
+        ctx.close()
+        if use_dist:
+            dist.destroy_process_group()
+        return 0
 
     # correctness of what was timed: the first and the last proof must pass the pairing verifier (publics = z[1 .. n_pub))
     def publics_of(j):
@@ -858,36 +929,8 @@ def main():
             "NTTs and the G2 accumulation running on other streams, so its own rate understates chip utilisation",
         }
 
-    out = {
-        "metric": "shielder_withdraw_groth16_proofs_per_sec_2^%d_constraints" % log_n,
-        "value": world * args.steps / elapsed,
-        "unit": "proofs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int: signed 28-bit limbs in 32-bit words, 64-bit column accumulators (Fr 255-bit / Fq 381-bit Montgomery)",
-        "data": "synthetic",
-        "config": {
-            "workload": "single withdraw-shaped Groth16 proof, N=2^%d (7 Fr NTTs, 4 G1 MSM + 1 G2 MSM of 2^%d-1 terms), 1 proof per step per GPU"
-            % (log_n, log_n),
-            "relation": "update_note (withdraw) with Poseidon-5 hashing, chain-padded to N" if args.relation == "poseidon"
-            else "hash-free chain stand-in",
-            "curve": "BLS12-381",
-            "independent_proofs_per_rank": args.steps,
-            "distinct_witnesses_per_rank": min(args.steps, n_distinct),
-            "fresh_r_s_per_proof": True,
-            "proofs_in_flight_per_gpu": 3,
-            # nothing is skipped: all five MSMs run in full; what is shared is the REDUCTION of the three queries that only
-            # ever appear summed in C (DESIGN.md 4.1) -- the proof bytes equal the oracle's prover's
-            "msm_schedule": "A | B1 (over r*z) + L + H reduced together | B2 (G2)",
-        },
+    out.update({
         "verified_by_pairing": bool(verified),
-        "setup_seconds": setup_s,
-        "proofs_in_flight": 3,
         "phase_ms_per_proof": {k: v[0] / args.steps for k, v in phases.items()},
         "roofline": roofline,
         "hip_versions": dict(zip(("build", "runtime"), z.hip_versions())),
@@ -896,7 +939,7 @@ def main():
         # (csrc/host_pool.hpp), CPU seconds per proof inside the timed region and the CPUs that keeps busy
         "host": dict(z.host_info(), host_cpu_s_per_proof=timed_region.cpu_s / max(1, args.steps),
                      host_cpus_busy=timed_region.cpu_s / elapsed if elapsed > 0 else None),
-    }
+    })
     if rank == 0 and not args.no_secondary:
         # PCIe-inclusive rate (SURVEY.md 8d "end-to-end proofs/s includes witness upload"): the same K proofs from
         # PINNED HOST witnesses; upload i+1 runs on the copy stream while proofs i-1 and i compute.  Never `value`.
@@ -966,6 +1009,7 @@ def main():
         saved = {k: getattr(pmc_traffic, k) for k in ("valu", "name", "total_valu", "source", "held_clock_ghz", "alone_ms", "upper_bound")}
         margs = argparse.Namespace(**vars(args))
         margs.steps, margs.warmup, margs.split, margs.msm_log_n = 2, 1, "points", 26
+        margs.dump_outputs = None  # (the outputs are the headline's)
         t0 = time.time()
         m26, rc26 = run_msm26(margs, pkg, z, ctx, 0, 1, False)
         for k, v in saved.items():

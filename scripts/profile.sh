@@ -16,7 +16,7 @@ STEPS_TRACE=${STEPS_TRACE:-48}
 STEPS_PMC=${STEPS_PMC:-3}
 mkdir -p "$OUT" "$DST"
 export TMPDIR=/tmp
-BENCH="python3 bench.py --warmup 1 --no-cpu-baseline --no-secondary --pmc-summary none"
+BENCH="python3 bench.py --full --warmup 1 --no-cpu-baseline --no-secondary --pmc-summary none"
 
 # 1. kernel trace + per-kernel statistics (durations of kernels on different streams overlap)
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- $BENCH --steps "$STEPS_TRACE" > "$OUT/trace.log" 2>&1
@@ -43,7 +43,7 @@ TRACE=$(find "$OUT/trace" -name '*_kernel_trace.csv' | head -1)
 python3 scripts/pmc_summary.py "$DST/pmc_summary_bench_steps${STEPS_PMC}.json" $((STEPS_PMC + 1)) "$OUT/pmc_fetch" "$OUT/pmc_write" "$OUT/pmc_sq" "$OUT/pmc_icache"
 grep -h '^{' "$OUT/trace.log" | tail -1 > "$DST/bench_line_under_trace.json"
 # the complete line again, now with traffic / instruction counts from the fresh PMC summary
-python3 bench.py --pmc-summary "$DST/pmc_summary_bench_steps${STEPS_PMC}.json" > "$DST/bench_line_full.json" 2> "$OUT/bench_full.err"
+python3 bench.py --full --pmc-summary "$DST/pmc_summary_bench_steps${STEPS_PMC}.json" > "$DST/bench_line_full.json" 2> "$OUT/bench_full.err"
 # 4. BASELINE configs[3] behind the bench contract (with its own PMC passes: HBM traffic and instruction count of the 2^26-term
 #    accumulation launch), and the torch-free twin of the headline run under the native HIP runtime
 MSM="python3 bench.py --workload msm26 --steps 1 --warmup 1 --msm-pmc-summary none"

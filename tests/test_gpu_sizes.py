@@ -395,13 +395,43 @@ def test_bench_msm26_workload_small():
     assert o["unit"] == "GB/s" and o["value"] > 0 and o["roofline"]["bound"] == "hbm" and 0 < o["roofline"]["frac"] < 1
 
 
+def test_bench_plain_run_reports_the_headline_and_dumps_the_last_proof(tmp_path):
+    """A plain `bench.py --steps K --warmup W` at the headline size does only the headline: its line carries the
+    contract's keys and none of what moved behind --full, and the whole process (start to exit) spends under 30 s
+    outside its K + W steps; --dump-outputs writes the last timed proof (192 bytes as float64), the same bytes on every
+    run with the same arguments, and the same proof the --full run times and verifies by pairing."""
+    import time
+
+    dumps = []
+    for i, extra in enumerate(([], [], ["--full", "--no-secondary", "--no-cpu-baseline"])):
+        d = tmp_path / ("out%d" % i)
+        t0 = time.perf_counter()
+        p, lines = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)] + extra)
+        wall = time.perf_counter() - t0
+        assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]
+        o = lines[0]
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+            assert key in o, key
+        assert o["steps"] == 3 and o["warmup"] == 1 and o["unit"] == "proofs/s" and o["value"] > 0
+        assert abs(o["value"] - 1e3 / o["ms_per_step"]) < 1e-6 * o["value"]
+        if extra:
+            assert o["verified_by_pairing"] is True and "roofline" in o
+        else:
+            assert not {"verified_by_pairing", "roofline", "cpu_baseline", "small_domain", "config4"} & set(o)
+            assert wall - (3 + 1) * o["ms_per_step"] / 1e3 < 30.0, (wall, o["ms_per_step"], o["setup_seconds"])
+        a = np.load(d / "proof.npy")
+        assert a.dtype == np.float64 and a.shape == (192,) and a.min() >= 0 and a.max() <= 255
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1]) and np.array_equal(dumps[0], dumps[2])
+
+
 def test_bench_gpus_gt_1_spawns_ranks_or_fails():
     """`python bench.py --gpus 2` without a launcher starts two fresh ranks.  With two GPUs the line must say
     n_gpus = 2; on a one-GPU box the second rank cannot bind a device and the whole command must fail without
     printing any line (round 2 printed an n_gpus = 1 line here)."""
     import torch
 
-    p, lines = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "14", "--no-secondary", "--no-cpu-baseline"])
+    p, lines = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "14", "--full", "--no-secondary", "--no-cpu-baseline"])
     assert "starting 2 ranks" in p.stderr
     if torch.cuda.device_count() >= 2:
         assert p.returncode == 0 and len(lines) == 1 and lines[0]["n_gpus"] == 2 and lines[0]["verified_by_pairing"] is True, p.stderr[-3000:]
@@ -417,7 +447,7 @@ def test_bench_multi_rank_path_as_a_shared_gpu_dry_run(world, workload):
     rank 0 alone emits ONE JSON line with every contract key, `cpu_baseline` included; the line is marked and its metric name
     cannot be mistaken for a scaling point.  LOCAL_WORLD_SIZE reaches the library: a rank's host threads = its share of
     the CPUs the box grants."""
-    args = ["--gpus", str(world), "--shared-gpu-dry-run", "--warmup", "1", "--no-secondary", "--cpu-sample-log-n", "14"]
+    args = ["--gpus", str(world), "--shared-gpu-dry-run", "--warmup", "1", "--full", "--no-secondary", "--cpu-sample-log-n", "14"]
     if workload == "proofs":
         args += ["--steps", "3", "--log-n", "14"]
     else:

@@ -469,11 +469,57 @@ int32_t zkmi_ark_vk_read(const uint8_t* buf, uint64_t len, int32_t compressed, u
                          uint32_t* out_n_pub, uint64_t* out_consumed);
 /* out may be NULL to query the size; *out_len receives the bytes needed / written */
 int32_t zkmi_ark_vk_write(const uint8_t* vk, uint32_t n_pub, int32_t compressed, uint8_t* out, uint64_t cap, uint64_t* out_len);
-/* proving key for `r1cs` from arkworks bytes (shape must match: n_vars, n_pub, domain); out_vk optional */
+/* proving key for `r1cs` from arkworks bytes (shape must match: n_vars, n_pub, domain); out_vk optional.
+ * The points are decompressed one by one on the host, and the queries are checked for curve membership only, never
+ * for the prime-order subgroups: a key that did not come from your own setup belongs in zkmi_ark_pk_load_validated
+ * below, which does both on the device. */
 int32_t zkmi_ark_pk_load(zkmi_ctx* ctx, const zkmi_r1cs* r1cs, const uint8_t* buf, uint64_t len, int32_t compressed,
                          int32_t check_curve, zkmi_pk** out_pk, uint8_t* out_vk, uint64_t vk_cap);
 int32_t zkmi_ark_pk_write(zkmi_ctx* ctx, const zkmi_pk* pk, const uint8_t* vk, int32_t compressed, uint8_t* out,
                           uint64_t cap, uint64_t* out_len);
+
+/* ---- point arrays parsed, decompressed and checked on the device (key and SRS ingest) ---------- *
+ * Three byte encodings of a BLS12-381 point, with exactly the acceptance rules of the host entry points
+ * (zkmi_g1_decompress, zkmi_bases_g1_load, zkmi_ark_pk_load, ...):
+ *   WIRE               this library's affine form: little-endian x | y (G2: x.c0 x.c1 y.c0 y.c1), 96 / 192 B,
+ *                      all zero = infinity, every coordinate < p
+ *   ZCASH_COMPRESSED   48 / 96 B big-endian, bit 7 set, infinity only as 0xC0 00.., bit 5 = y is the larger root
+ *   ZCASH_UNCOMPRESSED 96 / 192 B big-endian, bit 7 clear, infinity only as 0x40 00.., bit 5 clear
+ * checks: CURVE = y^2 = x^3 + b (a compressed point is on the curve or has no root: implied); SUBGROUP = [r]P = O,
+ * what arkworks' Validate::Yes and the zcash format ask of every point (implies CURVE). */
+#define ZKMI_ENC_WIRE 0
+#define ZKMI_ENC_ZCASH_COMPRESSED 1
+#define ZKMI_ENC_ZCASH_UNCOMPRESSED 2
+#define ZKMI_CHECK_CURVE 1
+#define ZKMI_CHECK_SUBGROUP 2
+/* per-element status bytes; an element with several faults reports the smallest */
+#define ZKMI_PT_OK 0
+#define ZKMI_PT_BAD_ENCODING 1    /* flag bits, non-canonical infinity, coordinate >= p */
+#define ZKMI_PT_NOT_ON_CURVE 2    /* no square root / curve equation fails */
+#define ZKMI_PT_NOT_IN_SUBGROUP 3
+/* n points in HBM (d_in 4-byte aligned) -> affine WIRE form in HBM (d_out_wire may be NULL: validate only);
+ * d_status: NULL or n bytes in HBM; *out_first_bad (optional): smallest failing index, UINT64_MAX when none.
+ * ZKMI_OK, or ZKMI_ERR_NON_CANONICAL when any element fails (d_out_wire is then unspecified at failing indices). */
+int32_t zkmi_g1_points_read_dev(zkmi_ctx* ctx, const void* d_in, uint64_t n, int32_t encoding, int32_t checks,
+                                void* d_out_wire, void* d_status, uint64_t* out_first_bad);
+int32_t zkmi_g2_points_read_dev(zkmi_ctx* ctx, const void* d_in, uint64_t n, int32_t encoding, int32_t checks,
+                                void* d_out_wire, void* d_status, uint64_t* out_first_bad);
+/* host bytes in any of the encodings -> resident bases, parsed / decompressed / checked on the device; a refused
+ * load returns ZKMI_ERR_NON_CANONICAL, leaves *out NULL and names the element in *out_first_bad (optional) */
+int32_t zkmi_bases_g1_load_encoded(zkmi_ctx* ctx, const uint8_t* points, uint64_t n, int32_t encoding, int32_t checks,
+                                   zkmi_bases_g1** out, uint64_t* out_first_bad);
+int32_t zkmi_bases_g2_load_encoded(zkmi_ctx* ctx, const uint8_t* points, uint64_t n, int32_t encoding, int32_t checks,
+                                   zkmi_bases_g2** out, uint64_t* out_first_bad);
+/* zkmi_ark_pk_load with every query point parsed on the device under `checks`; the verifying-key part, beta_g1 and
+ * delta_g1 are validated on the host (subgroup included).  out_where (optional): [0] = section of the refused point
+ * (0..4 = a, b_g1, b_g2, h, l; 5 = vk / beta_g1 / delta_g1), [1] = its index there (UINT64_MAX in section 5);
+ * UINT64_MAX twice when the refusal is not about a point.  A refused key returns ZKMI_ERR_NON_CANONICAL and leaves *out_pk NULL. */
+int32_t zkmi_ark_pk_load_validated(zkmi_ctx* ctx, const zkmi_r1cs* r1cs, const uint8_t* buf, uint64_t len,
+                                   int32_t compressed, int32_t checks, zkmi_pk** out_pk, uint8_t* out_vk,
+                                   uint64_t vk_cap, uint64_t out_where[2]);
+/* a key that is already resident (zkmi_pk_load, zkmi_groth16_setup): every query point on the device, the five single
+ * elements (section 5: alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2) on the host.  checks must not be 0. */
+int32_t zkmi_pk_check(zkmi_ctx* ctx, const zkmi_pk* pk, int32_t checks, uint64_t out_where[2]);
 
 /* ---- row a12: the reference's prove/verify surface ------------------------ */
 #define ZKMI_MERKLE_TREE_DEPTH 10 /* shielder/mocked_zk/src/lib.rs:16 */

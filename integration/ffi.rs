@@ -83,6 +83,11 @@ extern "C" {
     pub fn zkmi_groth16_setup(ctx: *mut zkmi_ctx, r1cs: *const zkmi_r1cs, toxic: *const u8, out_pk: *mut *mut zkmi_pk, vk_out: *mut u8, vk_cap: u64) -> i32;
     pub fn zkmi_ark_pk_load(ctx: *mut zkmi_ctx, r1cs: *const zkmi_r1cs, buf: *const u8, len: u64, compressed: i32, check_curve: i32,
                             out_pk: *mut *mut zkmi_pk, out_vk: *mut u8, vk_cap: u64) -> i32;
+    // for keys from outside: every query point parsed, decompressed and checked (checks: 1 = curve, 2 = + prime-order subgroup,
+    // arkworks' Validate::Yes) on the device; out_where = (section, index) of a refused point
+    pub fn zkmi_ark_pk_load_validated(ctx: *mut zkmi_ctx, r1cs: *const zkmi_r1cs, buf: *const u8, len: u64, compressed: i32, checks: i32,
+                                      out_pk: *mut *mut zkmi_pk, out_vk: *mut u8, vk_cap: u64, out_where: *mut u64) -> i32;
+    pub fn zkmi_pk_check(ctx: *mut zkmi_ctx, pk: *const zkmi_pk, checks: i32, out_where: *mut u64) -> i32;
     pub fn zkmi_ark_vk_read(buf: *const u8, len: u64, compressed: i32, out_vk: *mut u8, vk_cap: u64, out_n_pub: *mut u32, out_consumed: *mut u64) -> i32;
     pub fn zkmi_pk_shape(pk: *const zkmi_pk, n_vars: *mut u32, n_pub: *mut u32, log_n: *mut u32) -> i32;
     pub fn zkmi_host_info(out: *mut u32) -> i32;

@@ -15,4 +15,13 @@ from .binding import (  # noqa: F401
     lib_path,
     PHASES,
     ERR,
+    ENC_WIRE,
+    ENC_ZCASH_COMPRESSED,
+    ENC_ZCASH_UNCOMPRESSED,
+    CHECK_CURVE,
+    CHECK_SUBGROUP,
+    PT_OK,
+    PT_BAD_ENCODING,
+    PT_NOT_ON_CURVE,
+    PT_NOT_IN_SUBGROUP,
 )

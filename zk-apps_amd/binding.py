@@ -30,6 +30,11 @@ PHASES = {
     "witness": 6,
     "misc": 7,
 }
+# point encodings, checks and per-element status bytes of the device point readers (include/zkmi.h)
+ENC_WIRE, ENC_ZCASH_COMPRESSED, ENC_ZCASH_UNCOMPRESSED = 0, 1, 2
+CHECK_CURVE, CHECK_SUBGROUP = 1, 2
+PT_OK, PT_BAD_ENCODING, PT_NOT_ON_CURVE, PT_NOT_IN_SUBGROUP = 0, 1, 2, 3
+NO_INDEX = (1 << 64) - 1
 MERKLE_TREE_DEPTH = 10
 MAX_TREE_HEIGHT = 32
 TOKENS_NUMBER = 2
@@ -687,6 +692,43 @@ class Context:
         self._chk(self.lib.zkmi_bases_g2_load(self.h, _buf(affine), C.c_uint64(len(affine) // 192), C.c_int32(check), C.byref(h)))
         return Bases(self, h, 2, len(affine) // 192)
 
+    def _bases_encoded(self, group, points, encoding, checks):
+        w = (96 if group == 1 else 192) // (2 if encoding == ENC_ZCASH_COMPRESSED else 1)
+        h, bad = C.c_void_p(), C.c_uint64(NO_INDEX)
+        fn = self.lib.zkmi_bases_g1_load_encoded if group == 1 else self.lib.zkmi_bases_g2_load_encoded
+        rc = fn(self.h, _buf(points), C.c_uint64(len(points) // w), C.c_int32(encoding), C.c_int32(checks), C.byref(h), C.byref(bad))
+        if rc != 0:
+            err = ZkmiError(rc, (self.lib.zkmi_last_error(self.h) or b"").decode())
+            err.first_bad = None if bad.value == NO_INDEX else bad.value
+            raise err
+        return Bases(self, h, group, len(points) // w)
+
+    def bases_g1_encoded(self, points, encoding, checks=CHECK_SUBGROUP):
+        """Resident G1 bases from host bytes in any ENC_* form, parsed / decompressed / checked on the device.  A refused
+        load raises ZkmiError (NON_CANONICAL) whose `first_bad` is the smallest failing index."""
+        return self._bases_encoded(1, points, encoding, checks)
+
+    def bases_g2_encoded(self, points, encoding, checks=CHECK_SUBGROUP):
+        return self._bases_encoded(2, points, encoding, checks)
+
+    def _points_read_dev(self, group, d_in, n, encoding, checks, d_out_wire, d_status):
+        bad = C.c_uint64(NO_INDEX)
+        fn = self.lib.zkmi_g1_points_read_dev if group == 1 else self.lib.zkmi_g2_points_read_dev
+        rc = fn(self.h, C.c_void_p(d_in), C.c_uint64(n), C.c_int32(encoding), C.c_int32(checks),
+                C.c_void_p(d_out_wire) if d_out_wire else None, C.c_void_p(d_status) if d_status else None, C.byref(bad))
+        if rc not in (0, -2):
+            self._chk(rc)
+        assert (rc == 0) == (bad.value == NO_INDEX)
+        return None if rc == 0 else bad.value
+
+    def g1_points_read_dev(self, d_in, n, encoding, checks, d_out_wire=None, d_status=None):
+        """n G1 points at device address d_in in `encoding` -> affine wire form at d_out_wire (optional), one status byte
+        each at d_status (optional).  Returns None when every element passes, else the smallest failing index."""
+        return self._points_read_dev(1, d_in, n, encoding, checks, d_out_wire, d_status)
+
+    def g2_points_read_dev(self, d_in, n, encoding, checks, d_out_wire=None, d_status=None):
+        return self._points_read_dev(2, d_in, n, encoding, checks, d_out_wire, d_status)
+
     def bases_g1_synthetic_range(self, first, n):
         h = C.c_void_p()
         self._chk(self.z.tlib.zkmi_bases_g1_synthetic_range(self.h, C.c_uint64(first), C.c_uint64(n), C.byref(h)))
@@ -929,6 +971,22 @@ class Context:
                                             C.c_int32(int(check_curve)), C.byref(h), vk, C.c_uint64(cap)))
         return ProvingKey(self, h, r1cs), bytes(vk)
 
+    def ark_pk_load_validated(self, r1cs, buf, compressed, checks=CHECK_SUBGROUP):
+        """ark_pk_load for keys from outside: every query point is parsed and checked on the device under `checks`.
+        A refused key raises ZkmiError (NON_CANONICAL) whose `where` is (section, index) of the refused point, or None."""
+        h = C.c_void_p()
+        cap = 672 + 96 * r1cs.n_pub
+        vk = (C.c_uint8 * cap)()
+        where = (C.c_uint64 * 2)(NO_INDEX, NO_INDEX)
+        rc = self.lib.zkmi_ark_pk_load_validated(self.h, r1cs.h, _buf(buf), C.c_uint64(len(buf)), C.c_int32(int(compressed)),
+                                                 C.c_int32(checks), C.byref(h), vk, C.c_uint64(cap), where)
+        if rc != 0:
+            err = ZkmiError(rc, (self.lib.zkmi_last_error(self.h) or b"").decode())
+            err.where = None if where[0] == NO_INDEX else (int(where[0]), None if where[1] == NO_INDEX else int(where[1]))
+            assert not h.value
+            raise err
+        return ProvingKey(self, h, r1cs), bytes(vk)
+
     def ark_pk_write(self, pk, vk, compressed):
         need = C.c_uint64()
         self.lib.zkmi_ark_pk_write(self.h, pk.h, _buf(vk), C.c_int32(int(compressed)), None, C.c_uint64(0), C.byref(need))
@@ -1022,6 +1080,16 @@ class ProvingKey:
         out = (C.c_uint8 * (w * count))()
         self.ctx._chk(self.ctx.lib.zkmi_pk_export_query(self.ctx.h, self.h, C.c_int32(which), C.c_uint64(first), C.c_uint64(count), out))
         return bytes(out)
+
+    def check(self, checks=CHECK_SUBGROUP):
+        """zkmi_pk_check: every point of the resident key under `checks`.  None when all pass, else (section, index) of the
+        first refused point (sections 0..4 = a, b_g1, b_g2, h, l queries; 5 = alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2)."""
+        where = (C.c_uint64 * 2)(NO_INDEX, NO_INDEX)
+        rc = self.ctx.lib.zkmi_pk_check(self.ctx.h, self.h, C.c_int32(checks), where)
+        if rc == -2:
+            return int(where[0]), int(where[1])
+        self.ctx._chk(rc)
+        return None
 
     def schedule_state(self):
         """zkmi_pk_schedule_state: (B1 folded into the L + H reduction?, non-zero digits of the last finished proof's

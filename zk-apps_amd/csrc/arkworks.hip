@@ -14,6 +14,7 @@
 #include <string.h>
 #include <vector>
 #include "ctx.hpp"
+#include "points.hpp"
 
 using namespace zkmi;
 
@@ -101,8 +102,8 @@ bool read_vk(Reader& r, std::vector<uint8_t>* vk, uint32_t* n_pub) {
   for (uint64_t i = 0; i < n; i++)
     if (!r.g1(vk->data() + 672 + 96 * i)) return false;
   // arkworks' Validate::Yes also checks the prime-order subgroup; so does this library's verifier.  `check` asks for
-  // it here for the handful of points of a verifying key (the queries of a proving key are checked for curve
-  // membership only: an r-torsion check of 5 x 2^20 points on the host would take minutes)
+  // it here for the handful of points of a verifying key.  The queries of a proving key get that check on the device:
+  // zkmi_ark_pk_load_validated below (zkmi_ark_pk_load, the host path, checks them for curve membership only)
   if (r.check) {
     G1Affine a;
     G2Affine b;
@@ -181,6 +182,54 @@ int32_t zkmi_ark_pk_load(zkmi_ctx* ctx, const zkmi_r1cs* r1cs, const uint8_t* bu
   }
   return zkmi_pk_load(ctx, r1cs, vk.data(), beta_g1, vk.data() + 96, delta_g1, vk.data() + 480, q[0].data(), q[1].data(),
                       q[2].data(), q[3].data(), q[4].data(), out_pk);
+}
+
+// zkmi_ark_pk_load with the five queries handed to the device as they lie in the blob (points.hip): the host walks
+// the layout and checks the lengths, nothing more.  The verifying-key part, beta_g1 and delta_g1 stay on the host path.
+int32_t zkmi_ark_pk_load_validated(zkmi_ctx* ctx, const zkmi_r1cs* r1cs, const uint8_t* buf, uint64_t len,
+                                   int32_t compressed, int32_t checks, zkmi_pk** out_pk, uint8_t* out_vk,
+                                   uint64_t vk_cap, uint64_t out_where[2]) {
+  const int32_t enc = compressed ? ZKMI_ENC_ZCASH_COMPRESSED : ZKMI_ENC_ZCASH_UNCOMPRESSED;
+  if (!ctx || !r1cs || !buf || !out_pk || !point_args_ok(enc, &checks)) return ZKMI_ERR_BAD_ARG;
+  ZK_ENTER(ctx);
+  *out_pk = nullptr;
+  if (out_where) out_where[0] = out_where[1] = UINT64_MAX;
+  uint32_t n_vars = 0, n_pub = 0, nc = 0, log_n = 0;
+  int32_t rc = zkmi_r1cs_shape(r1cs, &n_vars, &n_pub, &nc, &log_n);
+  if (rc != ZKMI_OK) return rc;
+  Reader r{buf, len, compressed != 0, true};
+  std::vector<uint8_t> vk;
+  uint32_t vk_pub = 0;
+  if (!read_vk(r, &vk, &vk_pub)) {
+    if (out_where) out_where[0] = 5;
+    return ctx->fail(ZKMI_ERR_NON_CANONICAL, "arkworks key: verifying key part (section 5)");
+  }
+  if (vk_pub != n_pub) return ctx->fail(ZKMI_ERR_BAD_ARG, "arkworks key: number of instance variables differs from the relation");
+  uint8_t single[2][96];
+  for (int i = 0; i < 2; i++) {
+    G1Affine a;
+    if (!r.g1(single[i]) || ((checks & ZKMI_CHECK_SUBGROUP) && (!g1_from_wire(single[i], &a, true) || !g1_in_subgroup(a)))) {
+      if (out_where) out_where[0] = 5;
+      return ctx->fail(ZKMI_ERR_NON_CANONICAL, "arkworks key: beta_g1 / delta_g1 (section 5)");
+    }
+  }
+  const uint64_t N = 1ull << log_n;
+  const uint64_t want[5] = {n_vars, n_vars, n_vars, N - 1, n_vars - n_pub};
+  const uint8_t* q[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < 5; k++) {
+    uint64_t n = 0;
+    if (!r.len(&n)) return ctx->fail(ZKMI_ERR_NON_CANONICAL, "arkworks key: truncated");
+    if (n != want[k]) return ctx->fail(ZKMI_ERR_BAD_ARG, "arkworks key: query length differs from the relation's shape");
+    // the length prefix is untrusted: the bytes must be there before anything is allocated or uploaded for it
+    const uint64_t w = point_bytes(k == 2 ? 2 : 1, enc);
+    if (n > r.left / w || !r.take(n * w, &q[k])) return ctx->fail(ZKMI_ERR_NON_CANONICAL, "arkworks key: truncated");
+  }
+  if (out_vk) {
+    if (vk.size() > vk_cap) return ZKMI_ERR_BAD_ARG;
+    memcpy(out_vk, vk.data(), vk.size());
+  }
+  return pk_load_encoded(ctx, r1cs, vk.data(), single[0], vk.data() + 96, single[1], vk.data() + 480, q, enc, checks, out_pk,
+                         out_where);
 }
 
 int32_t zkmi_ark_pk_write(zkmi_ctx* ctx, const zkmi_pk* pk, const uint8_t* vk, int32_t compressed, uint8_t* out,

@@ -11,6 +11,7 @@
 #include "host_pool.hpp"
 #include "msm_pipe.hpp"
 #include "msm_impl.hpp"  // msm_combine_windows (host)
+#include "points.hpp"
 
 using namespace zkmi;
 
@@ -361,6 +362,76 @@ int32_t zkmi_bases_g2_load(zkmi_ctx* ctx, const uint8_t* affine, uint64_t n, int
   ZK_ENTER(ctx);
   return bases_load<zkmi_bases_g2, G2Affine, g2_from_wire, 192>(ctx, affine, n, check, out);
 }
+
+}  // extern "C"
+// host bytes in any encoding -> resident bases: the points are parsed, decompressed and checked by the kernels of
+// points.hip, which write the resident form themselves (no host conversion loop)
+template <class B, int GROUP>
+static int32_t bases_load_encoded(zkmi_ctx* ctx, const uint8_t* points, uint64_t n, int32_t enc, int32_t checks, B** out,
+                                  uint64_t* out_first_bad) {
+  if (!ctx || !points || !out || n == 0 || n >= (1ull << 31) || enc == PT_ENC_RESIDENT || !point_args_ok(enc, &checks))
+    return ZKMI_ERR_BAD_ARG;
+  ZK_ENTER(ctx);
+  *out = nullptr;
+  if (out_first_bad) *out_first_bad = UINT64_MAX;
+  B* b = new (std::nothrow) B();
+  if (!b) return ZKMI_ERR_BAD_ARG;
+  b->ctx = ctx;
+  b->n = n;
+  hipError_t e = hipMalloc(&b->d, sizeof(*b->d) * n);
+  if (e != hipSuccess) {
+    bases_destroy(b);
+    return ctx->hip_fail(e, "bases alloc");
+  }
+  uint64_t bad = UINT64_MAX;
+  uint32_t st = 0;
+  const int32_t rc = points_read_host(ctx, GROUP, points, n, enc, checks, b->d, &bad, &st);
+  if (rc != ZKMI_OK || bad != UINT64_MAX) {
+    bases_destroy(b);
+    if (rc != ZKMI_OK) return rc;
+    if (out_first_bad) *out_first_bad = bad;
+    return ctx->fail(ZKMI_ERR_NON_CANONICAL, "base point " + std::to_string(bad) + ": " + point_status_name(st));
+  }
+  if ((e = bases_finish(b, ctx->stream)) != hipSuccess) {
+    bases_destroy(b);
+    return ctx->hip_fail(e, "bases convert");
+  }
+  *out = b;
+  return ZKMI_OK;
+}
+extern "C" {
+int32_t zkmi_bases_g1_load_encoded(zkmi_ctx* ctx, const uint8_t* points, uint64_t n, int32_t encoding, int32_t checks,
+                                   zkmi_bases_g1** out, uint64_t* out_first_bad) {
+  return bases_load_encoded<zkmi_bases_g1, 1>(ctx, points, n, encoding, checks, out, out_first_bad);
+}
+int32_t zkmi_bases_g2_load_encoded(zkmi_ctx* ctx, const uint8_t* points, uint64_t n, int32_t encoding, int32_t checks,
+                                   zkmi_bases_g2** out, uint64_t* out_first_bad) {
+  return bases_load_encoded<zkmi_bases_g2, 2>(ctx, points, n, encoding, checks, out, out_first_bad);
+}
+
+static int32_t points_read_dev(zkmi_ctx* ctx, int group, const void* d_in, uint64_t n, int32_t enc, int32_t checks,
+                               void* d_out_wire, void* d_status, uint64_t* out_first_bad) {
+  if (!ctx || !d_in || n == 0 || n >= (1ull << 40) || enc == PT_ENC_RESIDENT || !point_args_ok(enc, &checks) ||
+      (reinterpret_cast<uintptr_t>(d_in) & 3u) || (reinterpret_cast<uintptr_t>(d_out_wire) & 3u))
+    return ZKMI_ERR_BAD_ARG;
+  ZK_ENTER(ctx);
+  uint64_t bad = UINT64_MAX;
+  uint32_t st = 0;
+  const int32_t rc = points_read(ctx, group, d_in, n, enc, checks, d_out_wire, false, d_status, &bad, &st);
+  if (rc != ZKMI_OK) return rc;
+  if (out_first_bad) *out_first_bad = bad;
+  if (bad != UINT64_MAX) return ctx->fail(ZKMI_ERR_NON_CANONICAL, "point " + std::to_string(bad) + ": " + point_status_name(st));
+  return ZKMI_OK;
+}
+int32_t zkmi_g1_points_read_dev(zkmi_ctx* ctx, const void* d_in, uint64_t n, int32_t encoding, int32_t checks,
+                                void* d_out_wire, void* d_status, uint64_t* out_first_bad) {
+  return points_read_dev(ctx, 1, d_in, n, encoding, checks, d_out_wire, d_status, out_first_bad);
+}
+int32_t zkmi_g2_points_read_dev(zkmi_ctx* ctx, const void* d_in, uint64_t n, int32_t encoding, int32_t checks,
+                                void* d_out_wire, void* d_status, uint64_t* out_first_bad) {
+  return points_read_dev(ctx, 2, d_in, n, encoding, checks, d_out_wire, d_status, out_first_bad);
+}
+
 int32_t zkmi_bases_g1_free(zkmi_bases_g1* b) {
   if (!b) return ZKMI_ERR_BAD_ARG;
   bases_destroy(b);

@@ -31,6 +31,7 @@
 #include "host_pool.hpp"
 #include "pairing.hpp"
 #include "r1cs.hpp"
+#include "points.hpp"
 
 namespace zkmi {
 
@@ -717,7 +718,104 @@ int32_t zkmi_pk_load(zkmi_ctx* ctx, const zkmi_r1cs* r, const uint8_t alpha_g1[9
 
 }  // extern "C"
 uint32_t zkmi::pk_tree_height(const zkmi_pk* pk) { return pk ? pk->tree_height : 0; }
+
+static const char* const PK_QUERY_NAME[5] = {"a_query", "b_g1_query", "b_g2_query", "h_query", "l_query"};
+
+// zkmi_pk_load with the queries still encoded: points.hip parses them on the device straight into the key's resident
+// arrays (l_query keeps its n_pub leading blanks, h_query its trailing one)
+int32_t zkmi::pk_load_encoded(zkmi_ctx* ctx, const zkmi_r1cs* r, const uint8_t alpha_g1[96], const uint8_t beta_g1[96],
+                              const uint8_t beta_g2[192], const uint8_t delta_g1[96], const uint8_t delta_g2[192],
+                              const uint8_t* const queries[5], int32_t enc, int32_t checks, zkmi_pk** out_pk,
+                              uint64_t where[2]) {
+  zkmi_pk* pk = new (std::nothrow) zkmi_pk();
+  if (!pk) return ZKMI_ERR_BAD_ARG;
+  hipError_t e = pk_alloc(pk, ctx, r);
+  if (e != hipSuccess) {
+    delete pk;
+    return ctx->hip_fail(e, "pk alloc");
+  }
+  const uint64_t N = 1ull << r->log_n, nv = r->n_vars, np = r->n_pub;
+  if (!(g1_from_wire(alpha_g1, &pk->alpha_g1, true) && g1_from_wire(beta_g1, &pk->beta_g1, true) &&
+        g1_from_wire(delta_g1, &pk->delta_g1, true) && g2_from_wire(beta_g2, &pk->beta_g2, true) &&
+        g2_from_wire(delta_g2, &pk->delta_g2, true))) {
+    delete pk;
+    if (where) where[0] = 5;
+    return ctx->fail(ZKMI_ERR_NON_CANONICAL, "proving key: alpha / beta / delta invalid");
+  }
+  if (np) e = hipMemset(pk->l_query, 0, sizeof(G1Affine) * np);
+  if (e == hipSuccess) e = hipMemset(pk->h_query + (N - 1), 0, sizeof(G1Affine));
+  struct {
+    int group;
+    void* dst;
+    uint64_t cnt;
+  } const sec[5] = {{1, pk->a_query, nv}, {1, pk->b_g1_query, nv}, {2, pk->b_g2_query, nv}, {1, pk->h_query, N - 1},
+                    {1, pk->l_query + np, nv - np}};
+  for (int k = 0; k < 5 && e == hipSuccess; k++) {
+    if (!sec[k].cnt) continue;
+    uint64_t bad = UINT64_MAX;
+    uint32_t st = 0;
+    const int32_t rc = points_read_host(ctx, sec[k].group, queries[k], sec[k].cnt, enc, checks, sec[k].dst, &bad, &st);
+    if (rc != ZKMI_OK || bad != UINT64_MAX) {
+      delete pk;
+      if (rc != ZKMI_OK) return rc;
+      if (where) where[0] = (uint64_t)k, where[1] = bad;
+      return ctx->fail(ZKMI_ERR_NON_CANONICAL, std::string("proving key: ") + PK_QUERY_NAME[k] + "[" + std::to_string(bad) +
+                                                   "] (section " + std::to_string(k) + "): " + point_status_name(st));
+    }
+  }
+  if (e == hipSuccess) e = hipMemcpy(&pk->a0, pk->a_query, sizeof(G1Affine), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&pk->b1_0, pk->b_g1_query, sizeof(G1Affine), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&pk->b2_0, pk->b_g2_query, sizeof(G2Affine), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = pk_convert_queries(pk);
+  if (e != hipSuccess) {
+    delete pk;
+    return ctx->hip_fail(e, "pk upload");
+  }
+  pk_build_delta_tables(pk);
+  *out_pk = pk;
+  return ZKMI_OK;
+}
+
 extern "C" {
+
+int32_t zkmi_pk_check(zkmi_ctx* ctx, const zkmi_pk* pk, int32_t checks, uint64_t out_where[2]) {
+  if (!ctx || !pk || checks == 0 || !point_args_ok(PT_ENC_RESIDENT, &checks)) return ZKMI_ERR_BAD_ARG;
+  ZK_ENTER(ctx);
+  if (ctx->device != pk->device) return ZKMI_ERR_BAD_ARG;
+  if (out_where) out_where[0] = out_where[1] = UINT64_MAX;
+  const bool sub = (checks & ZKMI_CHECK_SUBGROUP) != 0;
+  const G1Affine* s1[3] = {&pk->alpha_g1, &pk->beta_g1, &pk->delta_g1};
+  const G2Affine* s2[2] = {&pk->beta_g2, &pk->delta_g2};
+  for (uint64_t i = 0; i < 5; i++) {
+    const bool curve = i < 3 ? g1_on_curve(*s1[i]) : g2_on_curve(*s2[i - 3]);
+    const bool ok = curve && (!sub || (i < 3 ? g1_in_subgroup(*s1[i]) : g2_in_subgroup(*s2[i - 3])));
+    if (!ok) {
+      if (out_where) out_where[0] = 5, out_where[1] = i;
+      return ctx->fail(ZKMI_ERR_NON_CANONICAL, "proving key: single element " + std::to_string(i) + " (section 5): " +
+                                                   point_status_name(curve ? ZKMI_PT_NOT_IN_SUBGROUP : ZKMI_PT_NOT_ON_CURVE));
+    }
+  }
+  const uint64_t N = 1ull << pk->log_n, nv = pk->n_vars, np = pk->n_pub;
+  struct {
+    int group;
+    const void* src;
+    uint64_t cnt;
+  } const sec[5] = {{1, pk->a_query, nv}, {1, pk->b_g1_query, nv}, {2, pk->b_g2_query, nv}, {1, pk->h_query, N - 1},
+                    {1, pk->l_query + np, nv - np}};
+  for (int k = 0; k < 5; k++) {
+    if (!sec[k].cnt) continue;
+    uint64_t bad = UINT64_MAX;
+    uint32_t st = 0;
+    const int32_t rc = points_read(ctx, sec[k].group, sec[k].src, sec[k].cnt, PT_ENC_RESIDENT, checks, nullptr, false, nullptr, &bad, &st);
+    if (rc != ZKMI_OK) return rc;
+    if (bad != UINT64_MAX) {
+      if (out_where) out_where[0] = (uint64_t)k, out_where[1] = bad;
+      return ctx->fail(ZKMI_ERR_NON_CANONICAL, std::string("proving key: ") + PK_QUERY_NAME[k] + "[" + std::to_string(bad) +
+                                                   "] (section " + std::to_string(k) + "): " + point_status_name(st));
+    }
+  }
+  return ZKMI_OK;
+}
 
 int32_t zkmi_pk_free(zkmi_pk* pk) {
   if (!pk) return ZKMI_ERR_BAD_ARG;

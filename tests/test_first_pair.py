@@ -1,0 +1,224 @@
+"""The first pair of a bucket: the accumulation kernels add the entry behind a bucket's first finite entry with the
+affine + affine form (msm_impl.hpp madd_affine_pair, 4M + 2S) instead of the generic mixed addition.  These inputs put
+every exceptional case of that step into many buckets at once, in the windowed and in the shared-bucket (prepared bases)
+schedule, G1 and G2, and compare the MSM byte for byte with the C++ oracle:
+
+    P + P      both entries of a bucket are the same point with the same effective sign   -> redo list
+    P - P      the same point with opposite effective signs                               -> redo list
+    infinity   a base at infinity beside one finite entry (before it, behind it, between two finite entries)
+    load 1     one finite entry and nothing else: stored with ZZ = ZZZ = 1
+    load 2     two different points: the pair step is the bucket's only addition
+
+with the digit's sign on either entry (+ +, - -, + -, - +) and points given as P or as -P.  Every scalar has ONE designed
+signed digit d at position w (s = d 2^(c w); a negative digit is written 2^(c (w + 1)) - |d| 2^(c w), whose +1 digit lands
+in bucket 1 of the next position -- never a designed bucket, and in the shared schedule a heavy bucket of its own).  The
+order of a bucket's entries is the digit sort's business (LDS cursors), so the cases are designed and counted by bucket
+CONTENT: whichever entry comes first, a bucket of {P, P} meets P + P in the pair step.
+
+test_designed_inputs_hit_every_case_in_one_percent_of_the_buckets counts the cases from the signed-digit decomposition of
+the scalars alone (no GPU): each must hold at least 1 % of ALL buckets of the plan the library picks."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+from conftest import ROOT
+from oracle import bls12_381 as ec
+from oracle.bls12_381 import P, R
+
+EXP_LIB = os.path.join(ROOT, "zk-apps_amd", "libzkmi_exp.so")
+
+# a bucket's entries: (point 0 | 1 of the bucket or None = a base at infinity, base stored negated, digit negative)
+KINDS = [
+    ("pp", [(0, False, False), (0, False, False)]),
+    ("pp", [(0, False, True), (0, False, True)]),
+    ("pp", [(0, False, False), (0, True, True)]),  # P and -(-P)
+    ("pm", [(0, False, False), (0, False, True)]),
+    ("pm", [(0, False, True), (0, True, True)]),  # -P and -(-P)
+    ("inf", [(0, False, False), (None, False, True)]),  # infinity at the higher index
+    ("inf", [(None, False, False), (0, False, True)]),  # ... at the lower one
+    ("inf", [(0, False, False), (None, False, False), (1, False, True)]),  # ... between two finite entries
+    ("load1", [(0, False, False)]),
+    ("load1", [(0, False, True)]),
+    ("load2", [(0, False, False), (1, False, False)]),
+    ("load2", [(0, False, False), (1, False, True)]),
+    ("load2", [(0, False, True), (1, False, False)]),
+    ("load2", [(0, True, True), (1, False, True)]),
+]
+CASES = ("pp", "pm", "inf", "load1", "load2")
+
+
+def plan_of(zk, n, shared):
+    c, nd, parts, nb = zk.msm_plan_query(n, shared)[:4]
+    return {"c": c, "nd": nd, "buckets": parts * nb, "shared": shared}
+
+
+def design(n, plan):
+    """n terms [(point id or None, negated, scalar)] and the number of distinct points they use."""
+    c, nd, shared = plan["c"], plan["nd"], plan["shared"]
+    h = 1 << (c - 1)
+    wmax = nd - 2  # positions 0 .. wmax - 1: the carry of a negative digit stays below the top digit
+    assert wmax >= 1 and c * wmax <= 250
+    terms, npts, k = [], 0, 0
+
+    def slot(k):  # designed bucket number k -> (position, |digit|); |digit| in 2 .. h - 1
+        w, m = (k % wmax, 2 + k) if shared else (k % wmax, 2 + k // wmax)
+        assert m <= h - 1, "plan too small for this many designed buckets"
+        return w, m
+
+    def scalar(w, m, neg):
+        s = (1 << (c * (w + 1))) - (m << (c * w)) if neg else m << (c * w)
+        assert 0 < s < R
+        return s
+
+    while len(terms) < n:
+        _, entries = KINDS[k % len(KINDS)]
+        if len(terms) + len(entries) > n:
+            entries = [(0, False, k % 2 == 1)]  # fill up with buckets of one entry
+        w, m = slot(k)
+        for ref, negated, dneg in entries:
+            terms.append((None if ref is None else npts + ref, negated, scalar(w, m, dneg)))
+        npts += 1 + max((ref or 0) for ref, _, _ in entries)
+        k += 1
+    return terms, npts
+
+
+def signed_digits(s, c, nd):
+    """s = sum d_w 2^(c w) with d_w in [-(2^(c-1) - 1), 2^(c-1)]: the decomposition the digit sort makes (msm_sort.hip)."""
+    bias = (1 << (c - 1)) - 1
+    k = s + sum(bias << (c * w) for w in range(nd))
+    out = [((k >> (c * w)) & ((1 << c) - 1)) - bias for w in range(nd)]
+    assert k >> (c * nd) == 0 and sum(d << (c * w) for w, d in enumerate(out)) == s
+    return out
+
+
+def census(terms, plan):
+    """Buckets per case, by content: {case: count} over the plan's buckets."""
+    c, nd, shared = plan["c"], plan["nd"], plan["shared"]
+    buckets = {}
+    for pid, negated, s in terms:
+        for w, d in enumerate(signed_digits(s, c, nd)):
+            if d == 0:
+                continue
+            key = abs(d) if shared else (w, abs(d))
+            # the entry: which table / base point (shared: 2^(c w) P, so the position belongs to its identity), effective sign
+            ident = None if pid is None else ((pid, w) if shared else pid)
+            buckets.setdefault(key, []).append((ident, negated != (d < 0)))
+    out = dict.fromkeys(CASES, 0)
+    for ent in buckets.values():
+        fin = [e for e in ent if e[0] is not None]
+        if len(fin) < len(ent):
+            if 1 <= len(fin) <= 2:
+                out["inf"] += 1
+        elif len(ent) == 1:
+            out["load1"] += 1
+        elif len(ent) == 2:
+            (a, sa), (b, sb) = ent
+            out["load2" if a != b else "pp" if sa == sb else "pm"] += 1
+    return out
+
+
+def materialise(terms, points, width):
+    """Wire bytes of bases and scalars; points = wire bytes of the distinct points, width = 96 (G1) | 192 (G2)."""
+    half = width // 2
+
+    def neg(pt):  # y -> p - y per 48-byte component
+        ys = [(P - int.from_bytes(pt[half + 48 * i : half + 48 * i + 48], "little")) % P for i in range(half // 48)]
+        return pt[:half] + b"".join(y.to_bytes(48, "little") for y in ys)
+
+    bases, scalars = [], []
+    for pid, negated, s in terms:
+        pt = bytes(width) if pid is None else points[width * pid : width * pid + width]
+        bases.append(neg(pt) if negated and pid is not None else pt)
+        scalars.append(ec.fr_to_bytes(s))
+    return b"".join(bases), b"".join(scalars)
+
+
+# (group, terms): G1 in the plans of a few thousand terms; G2 also above 2^15 buckets per windowed plan, where the product
+# library's lone G2 MSM runs k_accum_g2_nc (below that it runs the two-pairs-per-bucket kernel)
+SIZES = [(1, 4000), (2, 4000), (2, 17000)]
+
+
+@pytest.mark.parametrize("group,n", SIZES)
+@pytest.mark.parametrize("shared", [False, True], ids=["windowed", "shared"])
+def test_designed_inputs_hit_every_case_in_one_percent_of_the_buckets(zk, group, n, shared):
+    plan = plan_of(zk, n, shared)
+    terms, npts = design(n, plan)
+    assert len(terms) == n and npts <= n
+    got = census(terms, plan)
+    print(plan, got)
+    for case in CASES:
+        assert got[case] * 100 >= plan["buckets"], (case, got, plan)
+
+
+def test_oracle_agrees_with_the_naive_sum_on_designed_inputs(zk):
+    """The C++ oracle's own exceptional cases, on a designed input small enough for Python's double-and-add."""
+    from oracle import cpp as ocpp
+
+    n = 3 * len(KINDS) + 5
+    plan = plan_of(zk, n, False)
+    terms, npts = design(n, plan)
+    pts = ec.synthetic_bases_g1(npts)
+    bases, scalars = materialise(terms, b"".join(ec.g1_to_bytes(p) for p in pts), 96)
+    want = None
+    for pid, negated, s in terms:
+        if pid is not None:
+            want = ec.pt_add(ec.Fq, want, ec.pt_mul(ec.Fq, ec.pt_neg(ec.Fq, pts[pid]) if negated else pts[pid], s))
+    assert ocpp.msm_g1(scalars, bases) == ec.g1_to_bytes(want)
+
+
+def check_group(zk, ctx, group, n):
+    """Windowed and shared-bucket MSM over the designed inputs against the C++ oracle (raises on a difference)."""
+    from oracle import cpp as ocpp
+
+    width = 96 if group == 1 else 192
+    for shared in (False, True):
+        plan = plan_of(zk, n, shared)
+        terms, npts = design(n, plan)
+        got = census(terms, plan)
+        assert all(got[case] * 100 >= plan["buckets"] for case in CASES), (got, plan)
+        src = ctx.bases_g1_synthetic(npts) if group == 1 else ctx.bases_g2_synthetic(npts)
+        points = src.read(0, npts)
+        src.free()
+        bases, scalars = materialise(terms, points, width)
+        want = (ocpp.msm_g1 if group == 1 else ocpp.msm_g2)(scalars, bases)
+        b = (ctx.bases_g1 if group == 1 else ctx.bases_g2)(bases)
+        if shared:
+            b.prepare()
+        have = (ctx.msm_g1 if group == 1 else ctx.msm_g2)(scalars, b)
+        b.free()
+        assert have == want, (group, n, "shared" if shared else "windowed", have.hex(), want.hex())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("group,n", SIZES)
+def test_first_pair_cases_match_the_cpp_oracle(zk, ctx, group, n):
+    check_group(zk, ctx, group, n)
+
+
+_CHILD = r"""
+import sys
+sys.path[:0] = [%r, %r]
+import test_first_pair as t
+from zkmi_loader import load_pkg
+z = load_pkg().Zkmi(%r)
+ctx = z.context(0)
+for group in (1, 2):
+    t.check_group(z, ctx, group, 4000)
+ctx.close()
+print("first pair ok")
+"""
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env", [{"ZKMI_SOLO_SPLIT_G2": "0"}, {"ZKMI_FORCE_MULTI": "1", "ZKMI_SOLO_SPLIT": "0", "ZKMI_SOLO_SPLIT_G2": "0"}],
+                         ids=["g2_nc", "multi_form"])
+def test_first_pair_cases_in_the_one_lane_kernels_at_small_sizes(env):
+    """Below 2^15 (G2) / 2^16 (G1 multi form) buckets a lone MSM of the product library runs the two-lanes-per-bucket kernels.
+    The A/B library's switches send the same small inputs through k_accum_g2_nc and through the multi form of
+    k_accum_g1_nc, the kernels of the prover's pipeline (a child process: the switches are read once per process)."""
+    assert os.path.exists(EXP_LIB), "zk-apps_amd/libzkmi_exp.so missing: run __graft_entry__.build() (make experiments)"
+    code = _CHILD % (ROOT, os.path.join(ROOT, "tests"), EXP_LIB)
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, **env))
+    assert p.returncode == 0 and "first pair ok" in p.stdout, (env, p.stdout[-1500:], p.stderr[-3000:])

@@ -118,6 +118,24 @@ __device__ __forceinline__ bool madd_generic(XYZZ<F>& acc, const Affine<F>& p, u
   acc.y = f_mul_sub_mul(r, f_sub_lazy(q, acc.x), acc.y, ppp);
   return true;
 }
+// The same for an accumulator that is still ONE affine point (x, y set; zz = zzz = 1 implied and never read): EFD "xyzz"
+// mmadd-2008-s, 4M + 2S.  madd_generic would multiply p.x, p.y, pp and ppp by one here: four products of the ten, once per
+// bucket.  Same contract (false: p = +-acc, nothing written) and the same lazy differences; sets all four coordinates.
+template <class F>
+__device__ __forceinline__ bool madd_affine_pair(XYZZ<F>& acc, const Affine<F>& p, uint32_t negmask = 0) {
+  F pp_ = f_sub_lazy(p.x, acc.x);
+  F r = f_signed_sub_lazy(p.y, negmask, acc.y);
+  F pp = pp_.sqr();
+  F rr = r.sqr();
+  if (pp.is_zero()) return false;
+  F ppp = pp_ * pp;
+  F q = acc.x * pp;
+  acc.x = f_x3(rr, ppp, q);
+  acc.y = f_mul_sub_mul(r, f_sub_lazy(q, acc.x), acc.y, ppp);
+  acc.zz = pp;
+  acc.zzz = ppp;
+  return true;
+}
 // device table entries at infinity are exact zeros (k_bases_convert, k_build_table); one limb decides for all but
 // 2^-28 of the finite entries, the full test runs behind that branch
 template <class P>
@@ -172,7 +190,7 @@ struct AccumArgs<F, true> {
 // test of its own: with acc = (0, 0, 0, 0) the first addition computes P = x zz - X = 0, which is the "needs the complete
 // group law" exit below -- the bucket goes to the redo pass, whose complete addition starts from infinity.
 // (Any early exit through the redo list IN FRONT of the loop made the register allocator spill 120 dwords inside the
-// loop; this form spills 24 -- the plain kernel's 0 is a lucky draw at exactly the 168 registers of three waves per SIMD.)
+// loop; with the one exit behind the count-down loop below this form spills 3, and the plain kernel needs 166 registers.)
 template <class F, int W, int BW, bool MULTI = false, bool INTO = false>
 __global__ void __launch_bounds__(64 * BW, W)
 k_accum_g1_nc(const AccumArgs<F, MULTI> args, uint32_t total_buckets) {
@@ -222,34 +240,67 @@ k_accum_g1_nc(const AccumArgs<F, MULTI> args, uint32_t total_buckets) {
     }
     if (v >> 31) p.y = p.y.neg();
     acc.x = p.x;
-    acc.y = p.y;
-    acc.zz = F::one();
-    acc.zzz = F::one();
+    acc.y = p.y;  // (zz = zzz = 1 are set below, where the entry behind this one does not make them)
     j++;
     break;
   }
+  bool bad = false;  // doubling or cancellation met: the bucket goes to the redo list
   uint32_t v_cur = 0, v_next = 0;
   if (j < end) {
     v_cur = sorted[j];
     fetch(v_cur);
     if (j + 1 < end) v_next = sorted[j + 1];
   }
-  for (; j < end; j++) {
+  if constexpr (!INTO) {
+    // The entry behind the first meets an accumulator that is still affine: madd_affine_pair, 4M + 2S.  Lanes of a wave own
+    // buckets of near-equal load, so the wave takes this step together.  It is one peeled iteration of the loop below (same
+    // tile, same prefetch), not a loop of its own: an entry at infinity HERE (exceptional) leaves zz = zzz = 1 and the
+    // generic additions take over.  A search loop for "the next finite entry" spilt 144 - 228 bytes per lane.
+    bool paired = false;
+    if (j < end) {
+      Affine<F> p;
+      take(p);
+      const uint32_t v = v_cur;
+      if (j + 1 < end) {
+        fetch(v_next);
+        v_cur = v_next;
+        if (j + 2 < end) v_next = sorted[j + 2];
+      }
+      j++;
+      if (!affine_is_zero_words(p)) {
+        bad = !madd_affine_pair(acc, p, 0u - (v >> 31));
+        paired = true;
+      }
+    }
+    if (!paired) {
+      acc.zz = F::one();
+      acc.zzz = F::one();
+    }
+    if (bad) j = end;
+  }
+  // ONE exit behind the loop for both outcomes, and a count-down instead of (j, end): with a return to the redo list inside
+  // the loop or in front of it the register allocator spilt 12 - 124 bytes per lane around the pair step; this form needs
+  // 166 registers and no scratch (tests/test_cpu_host.py::test_kernel_register_budgets holds it to that).
+  const uint32_t* sp = sorted + j;
+  for (uint32_t rem = end - j; rem > 0; rem--, sp++) {
     Affine<F> p;
     take(p);
     const uint32_t v = v_cur;
-    if (j + 1 < end) {
+    if (rem > 1) {
       fetch(v_next);
       v_cur = v_next;
-      if (j + 2 < end) v_next = sorted[j + 2];
+      if (rem > 2) v_next = sp[2];
     }
     if (affine_is_zero_words(p)) continue;
     if (!madd_generic(acc, p, 0u - (v >> 31))) {
-      // doubling or cancellation: k_accum_redo recomputes the bucket (INTO: from the value it still holds -- nothing
-      // has been written)
-      redo[1 + atomicAdd(redo, 1u)] = b;
-      return;
+      bad = true;
+      break;
     }
+  }
+  if (bad) {
+    // k_accum_redo recomputes the bucket (INTO: from the value it still holds -- nothing has been written)
+    redo[1 + atomicAdd(redo, 1u)] = b;
+    return;
   }
   store_vec(buckets + b, acc);
 }
@@ -257,6 +308,13 @@ k_accum_g1_nc(const AccumArgs<F, MULTI> args, uint32_t total_buckets) {
 }  // namespace zkmi
 #include "msm_impl_exp.hpp"  // retired kernel generations: A/B library only
 namespace zkmi {
+// TIMING ONLY (ZKMI_GATHER_MASK_BITS = k > 0): every table index of a sort is cut to its low k bits before the accumulation
+// reads it, so that all gathers hit a sub-table of 2^k entries that stays in L2.  The sums are WRONG by design: what is left
+// of a launch's time and held clock is the arithmetic alone, the bound of what any change to the fetch path can give.
+template <int UNUSED = 0>
+__global__ void k_mask_sorted(uint32_t* __restrict__ sorted, uint64_t n, uint32_t keep) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) sorted[i] &= keep;
+}
 #endif
 // acc += o for acc, o != O; false when the sum needs the complete group law (o = +-acc): same contract as madd_generic
 template <class F>
@@ -419,16 +477,30 @@ k_accum_g2_nc(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __restri
     if (load_point(v, p)) continue;
     acc.x = p.x;
     acc.y = (v >> 31) ? p.y.neg() : p.y;
-    acc.zz = Fq2P::one();
-    acc.zzz = Fq2P::one();
     j++;
     break;
+  }
+  // the next finite entry meets an accumulator that is still affine: 4M + 2S (madd_affine_pair)
+  bool paired = false;
+  for (; j < end && !paired; j++) {
+    Affine<Fq2P> p;
+    const uint32_t v = sorted[j];
+    if (load_point(v, p)) continue;
+    if (!madd_affine_pair(acc, p, 0u - (v >> 31))) {  // pair-uniform (Fq2P::is_zero exchanges the halves)
+      if (comp == 0) redo[1 + atomicAdd(redo, 1u)] = b;
+      return;
+    }
+    paired = true;
+  }
+  if (!paired) {  // one finite entry
+    acc.zz = Fq2P::one();
+    acc.zzz = Fq2P::one();
   }
   for (; j < end; j++) {
     Affine<Fq2P> p;
     const uint32_t v = sorted[j];
     if (load_point(v, p)) continue;
-    if (!madd_generic(acc, p, 0u - (v >> 31))) {  // pair-uniform (Fq2P::is_zero exchanges the halves)
+    if (!madd_generic(acc, p, 0u - (v >> 31))) {  // pair-uniform
       if (comp == 0) redo[1 + atomicAdd(redo, 1u)] = b;
       return;
     }
@@ -732,8 +804,6 @@ k_accum_heavy_nc(const Affine<F>* __restrict__ bases, const uint32_t* __restrict
       if (v >> 31) p.y = p.y.neg();
       acc.x = p.x;
       acc.y = p.y;
-      acc.zz = F::one();
-      acc.zzz = F::one();
       have = true;
       j += 64;
       break;
@@ -748,7 +818,28 @@ k_accum_heavy_nc(const Affine<F>* __restrict__ bases, const uint32_t* __restrict
       fetch(v_cur);
       if (j + 64 < w1) v_next = sorted[j + 64];
     }
-    bool bad = false;
+    // the lane's entry behind the first meets a sum that is still affine: madd_affine_pair (k_accum_g1_nc's peeled iteration)
+    bool bad = false, paired = false;
+    if (j < w1) {
+      Affine<F> p;
+      take(p);
+      const uint32_t v = v_cur;
+      if (j + 64 < w1) {
+        fetch(v_next);
+        v_cur = v_next;
+        if (j + 128 < w1) v_next = sorted[j + 128];
+      }
+      j += 64;
+      if (!affine_is_zero_words(p)) {
+        bad = !madd_affine_pair(acc, p, 0u - (v >> 31));
+        paired = true;
+      }
+    }
+    if (!paired) {
+      acc.zz = F::one();
+      acc.zzz = F::one();
+    }
+    if (bad) j = w1;  // k_accum_heavy recomputes this lane's <= PL points with the complete law
     for (; j < w1; j += 64) {
       Affine<F> p;
       take(p);
@@ -760,7 +851,7 @@ k_accum_heavy_nc(const Affine<F>* __restrict__ bases, const uint32_t* __restrict
       }
       if (affine_is_zero_words(p)) continue;
       if (!madd_generic(acc, p, 0u - (v >> 31))) {
-        bad = true;  // k_accum_heavy recomputes this lane's <= PL points with the complete law
+        bad = true;
         break;
       }
     }
@@ -807,21 +898,29 @@ k_accum_heavy_nc_g2(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __
       if (load_point(v, p)) continue;
       acc.x = p.x;
       acc.y = (v >> 31) ? p.y.neg() : p.y;
-      acc.zz = Fq2P::one();
-      acc.zzz = Fq2P::one();
       have = true;
       j += 32;
       break;
     }
     if (have) {
-      for (; j < w1; j += 32) {
+      // the pair's next finite entry meets a sum that is still affine: 4M + 2S (madd_affine_pair)
+      bool paired = false;
+      for (; j < w1 && !paired && !bad; j += 32) {
         Affine<Fq2P> p;
         const uint32_t v = sorted[j];
         if (load_point(v, p)) continue;
-        if (!madd_generic(acc, p, 0u - (v >> 31))) {  // pair-uniform
-          bad = true;
-          break;
-        }
+        if (madd_affine_pair(acc, p, 0u - (v >> 31))) paired = true;  // pair-uniform
+        else bad = true;
+      }
+      if (!paired) {  // one finite entry (or bad: the marker is stored below)
+        acc.zz = Fq2P::one();
+        acc.zzz = Fq2P::one();
+      }
+      for (; j < w1 && !bad; j += 32) {
+        Affine<Fq2P> p;
+        const uint32_t v = sorted[j];
+        if (load_point(v, p)) continue;
+        if (!madd_generic(acc, p, 0u - (v >> 31))) bad = true;  // pair-uniform
       }
     }
     if (!have || bad) {
@@ -1640,6 +1739,12 @@ hipError_t MsmEngine<F>::run_device_multi(const MsmSort* const* sorts, const Aff
                            0xffffffffu, (const uint32_t*)nullptr, pool_nc);
     }
   };
+#ifdef ZKMI_EXPERIMENTS
+  if (const int mask_bits = ZK_TUNE("ZKMI_GATHER_MASK_BITS", 0); mask_bits > 0 && mask_bits < 31)
+    for (int m = 0; m < nm; m++)  // (all cap_entries words of the buffer: idempotent, and a sort may serve several MSMs)
+      hipLaunchKernelGGL(k_mask_sorted<0>, dim3(1024), dim3(256), 0, st, sorts[m]->sorted, sorts[m]->cap_entries,
+                         0x80000000u | ((1u << mask_bits) - 1u));
+#endif
   for (int m = 0; m < nm; m++) {
     slot_plan[slots[m]] = sorts[m]->plan;
     const hipStream_t st_reduce = st_reduces[m];

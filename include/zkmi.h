@@ -228,6 +228,11 @@ int32_t zkmi_g2_generator(uint8_t out_affine[192]);
 /* reduced optimal-ate pairing e(P,Q) as 12 x 48-byte LE Fq coefficients in the
  * tower basis c0.c0.c0, c0.c0.c1, c0.c1.c0, ... (Fq12 = Fq6[w], Fq6 = Fq2[v]) */
 int32_t zkmi_pairing(const uint8_t g1_affine[96], const uint8_t g2_affine[192], uint8_t out_fq12[576]);
+/* prod_i e(P_i, Q_i) for n pairs in HBM: d_g1 = n x 96 B, d_g2 = n x 192 B, affine WIRE form (all zero = infinity;
+ * a pair with an infinite member contributes 1).  Miller loops and their product on the device, ONE final
+ * exponentiation on the host.  out_fq12: the 576 bytes zkmi_pairing writes.  The points must be in the r-order
+ * subgroups (the caller's duty here, as for zkmi_pairing; use zkmi_g{1,2}_points_read_dev). n = 0: out = 1. */
+int32_t zkmi_pairing_product_dev(zkmi_ctx* ctx, const void* d_g1, const void* d_g2, uint64_t n, uint8_t out_fq12[576]);
 
 /* ---- rows a1-a5, a7: relation + witness ---------------------------------- */
 /* R1CS in CSR form; column 0 is the constant 1, columns [0, n_pub) are the
@@ -458,6 +463,41 @@ int32_t zkmi_groth16_prove_batch_multi(zkmi_ctx* const* ctxs, const zkmi_pk* con
  * encodings (one encoding of infinity) of points in the r-order subgroups, and so must the vk's points;
  * anything else returns ZKMI_ERR_NON_CANONICAL, a failed pairing equation ZKMI_ERR_VERIFICATION. */
 int32_t zkmi_groth16_verify(const uint8_t* vk, uint32_t n_pub, const uint8_t* publics, const uint8_t proof[192]);
+
+/* A verifying key validated ONCE (host only, no context): exactly the checks zkmi_groth16_verify makes on its vk
+ * argument at every call -- canonical wire form, curve, subgroup of alpha, beta, gamma, delta and every gamma_abc.
+ * ZKMI_ERR_NON_CANONICAL on a refused key (*out stays NULL). */
+typedef struct zkmi_vk zkmi_vk;
+int32_t zkmi_vk_prepare(const uint8_t* vk, uint32_t n_pub, zkmi_vk** out);
+int32_t zkmi_vk_free(zkmi_vk* vk);
+
+/* Batch verification of n proofs of ONE key: the points are decompressed and subgroup-checked on the device, and one
+ * random linear combination of the n pairing equations is checked with n + 3 Miller loops on the device and ONE final
+ * exponentiation,
+ *   prod_i e(w_i A_i, B_i) * e(-(sum w_i) alpha, beta) * e(-sum_i w_i X_i, gamma) * e(-sum_i w_i C_i, delta) = 1,
+ *   X_i = ic_0 + sum_j pub_ij ic_j.
+ * proofs: n x 192 B (host); publics: n x (n_pub - 1) x 32 B (host).
+ * weights: n x 16 B little-endian, each non-zero, drawn uniformly by the caller -- or NULL: the library draws them from
+ * the OS (getrandom).  Explicit for the reason r and s are explicit in the prover: reproducible runs.
+ * Accepts iff every proof would be accepted by zkmi_groth16_verify, up to a false accept with probability <= 2^-128
+ * over the weights.  ZKMI_OK / ZKMI_ERR_NON_CANONICAL (some proof malformed) / ZKMI_ERR_VERIFICATION (all well formed,
+ * some equation fails).  out_status (optional, n bytes): per proof; out_first_bad (optional): smallest failing index,
+ * UINT64_MAX when none.  n = 0: ZKMI_OK.  A zero weight: ZKMI_ERR_BAD_ARG before anything is launched.
+ * A malformed proof (status 1-4) is left out of the product, the others are still checked.  When the product over the
+ * well-formed proofs is not 1 and out_status is given, the failing proofs are found by bisection: the per-proof Miller
+ * values e(w_i A_i, B_i) are kept, a subset costs three scalar sums, three Miller loops and one final exponentiation.
+ * Worst case (every proof bad): 2 n - 1 subsets, i.e. about 2 n final exponentiations -- as slow as the host loop;
+ * k bad proofs cost at most about 2 k log2(n) subsets.  With neither out_status nor out_first_bad the call returns
+ * after the first verdict (out_first_bad alone still needs the localisation to name the smallest failing index). */
+#define ZKMI_PROOF_OK 0
+#define ZKMI_PROOF_BAD_ENCODING 1     /* = ZKMI_PT_* of the first faulty point among A, B, C */
+#define ZKMI_PROOF_NOT_ON_CURVE 2
+#define ZKMI_PROOF_NOT_IN_SUBGROUP 3
+#define ZKMI_PROOF_BAD_PUBLIC 4       /* a public input >= r */
+#define ZKMI_PROOF_PAIRING 5          /* well formed, the equation does not hold */
+int32_t zkmi_groth16_verify_batch(zkmi_ctx* ctx, const zkmi_vk* vk, uint64_t n, const uint8_t* publics,
+                                  const uint8_t* proofs, const uint8_t* weights, uint8_t* out_status,
+                                  uint64_t* out_first_bad);
 
 /* ---- keys in arkworks' CanonicalSerialize layout (drop-in for keys made by ark-groth16) -------- *
  * VerifyingKey = alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | Vec<gamma_abc_g1>;

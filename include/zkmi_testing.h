@@ -40,6 +40,15 @@ int32_t zkmi_selftest_fq28(uint64_t seed, uint32_t iters, uint32_t* out_mismatch
 int32_t zkmi_selftest_assembly(uint64_t seed, uint32_t iters, uint32_t* out_mismatches);
 int32_t zkmi_selftest_host_pool(uint32_t callers, uint32_t jobs, uint32_t* out_mismatches);
 int32_t zkmi_selftest_poseidon(int32_t field, uint64_t seed, uint32_t iters, uint32_t* out_mismatches);
+/* The Miller loop the device runs (csrc/pairing_dev.hip: Jacobian T, scaled sparse lines, complex squaring, one merged loop)
+ * instantiated over the HOST field types: conj, final exponentiation, the 576 bytes of zkmi_pairing.  Pins the formulas
+ * against pairing.hip's affine loop without a GPU. */
+int32_t zkmi_selftest_miller_formulas(const uint8_t g1_affine[96], const uint8_t g2_affine[192], uint8_t out_fq12[576]);
+/* Where the last zkmi_groth16_verify_batch of this library spent its time, in ms of host clock, the stream waited for at
+ * every boundary (the product library neither waits there nor records): [0] upload and split, [1] decompression and
+ * subgroup checks, [2] w_i A_i and the MSM bases, [3] the n Miller loops, [4] the three sums (host Fr, MSM, scalar
+ * multiplications), [5] three Miller loops and the products, [6] final exponentiations; [4]-[6] summed over all ranges. */
+int32_t zkmi_verify_batch_phases(double out_ms[7]);
 /* Device self-test of the quad-split complete addition (csrc/quad.hpp: one coordinate of an XYZZ point per lane of a quad)
  * against curve.hpp's one-lane addition on the device and the 32-bit-limb host arithmetic: n pairs with every special case
  * (o = a, o = -a, either at infinity, equal points in different representations), and 16-point sums over the quads of a wave. */

@@ -24,6 +24,7 @@ pub const ZKMI_MAX_TREE_HEIGHT: usize = 32;
 #[repr(C)] pub struct zkmi_bases_g1 { _p: [u8; 0] }
 #[repr(C)] pub struct zkmi_bases_g2 { _p: [u8; 0] }
 #[repr(C)] pub struct zkmi_comm { _p: [u8; 0] }
+#[repr(C)] pub struct zkmi_vk { _p: [u8; 0] }
 
 /// = `Scalar { bytes: [u8; 32] }` (mocked_zk/src/scalar.rs:1-6), little-endian
 #[repr(C)] #[derive(Clone, Copy)] pub struct zkmi_scalar { pub bytes: [u8; 32] }
@@ -105,6 +106,14 @@ extern "C" {
                                           z: *const *const core::ffi::c_void, z_on_device: i32, r: *const u8, s: *const u8,
                                           out_proofs: *mut u8) -> i32;
     pub fn zkmi_groth16_verify(vk: *const u8, n_pub: u32, publics: *const u8, proof: *const u8) -> i32;
+    // batch verification: the key validated once, n proofs under one random linear combination (per-proof status bytes
+    // ZKMI_PROOF_*: 0 ok, 1-3 = the point status of A / B / C, 4 = public input >= r, 5 = pairing equation)
+    pub fn zkmi_vk_prepare(vk: *const u8, n_pub: u32, out: *mut *mut zkmi_vk) -> i32;
+    pub fn zkmi_vk_free(vk: *mut zkmi_vk) -> i32;
+    pub fn zkmi_groth16_verify_batch(ctx: *mut zkmi_ctx, vk: *const zkmi_vk, n: u64, publics: *const u8, proofs: *const u8,
+                                     weights: *const u8, out_status: *mut u8, out_first_bad: *mut u64) -> i32;
+    pub fn zkmi_pairing_product_dev(ctx: *mut zkmi_ctx, d_g1: *const core::ffi::c_void, d_g2: *const core::ffi::c_void, n: u64,
+                                    out_fq12: *mut u8) -> i32;
 
     // the mock's own surface, bit for bit (row a12) — lets call sites migrate one at a time
     pub fn zkmi_account_new(tokens: *const zkmi_scalar, out: *mut zkmi_account) -> i32;

@@ -362,6 +362,14 @@ class Zkmi:
             return False
         raise ZkmiError(rc)
 
+    def vk_prepare(self, vk):
+        """zkmi_vk_prepare: the verifying key validated once (what zkmi_groth16_verify re-checks at every call), for
+        Context.groth16_verify_batch.  A refused key raises ZkmiError (NON_CANONICAL)."""
+        n_pub = (len(vk) - 672) // 96
+        h = C.c_void_p()
+        self._chk(self.lib.zkmi_vk_prepare(_buf(vk), C.c_uint32(n_pub), C.byref(h)))
+        return PreparedVk(self, h, n_pub)
+
     # ---- R1CS ---------------------------------------------------------------
     def shielder_r1cs(self, log_n):
         h = C.c_void_p()
@@ -640,6 +648,18 @@ class Comm:
             self.h = None
 
 
+class PreparedVk:
+    """zkmi_vk: a validated verifying key (host memory only)."""
+
+    def __init__(self, z, h, n_pub):
+        self.z, self.h, self.n_pub = z, h, n_pub
+
+    def free(self):
+        if self.h:
+            self.z.lib.zkmi_vk_free(self.h)
+            self.h = None
+
+
 class Context:
     """One HIP device + stream + resident workspaces (zkmi_ctx)."""
 
@@ -728,6 +748,28 @@ class Context:
 
     def g2_points_read_dev(self, d_in, n, encoding, checks, d_out_wire=None, d_status=None):
         return self._points_read_dev(2, d_in, n, encoding, checks, d_out_wire, d_status)
+
+    def pairing_product_dev(self, d_g1, d_g2, n):
+        """prod_i e(P_i, Q_i) of n pairs in HBM (affine wire form, subgroup points): the 576 bytes Zkmi.pairing returns."""
+        out = (C.c_uint8 * 576)()
+        self._chk(self.lib.zkmi_pairing_product_dev(self.h, C.c_void_p(d_g1) if d_g1 else None, C.c_void_p(d_g2) if d_g2 else None,
+                                                    C.c_uint64(n), out))
+        return bytes(out)
+
+    def groth16_verify_batch(self, vk, publics, proofs, weights=None, want_status=True):
+        """zkmi_groth16_verify_batch over host bytes: vk from Zkmi.vk_prepare, proofs n x 192 B, publics n x (n_pub - 1) x 32 B,
+        weights n x 16 B or None (drawn from the OS).  Returns (ok, status bytes or None, first_bad or None); a rejected
+        batch is a result, not an exception.  Anything else (bad argument, HIP error) raises ZkmiError."""
+        n = len(proofs) // 192
+        assert len(proofs) == 192 * n and len(publics) == 32 * (vk.n_pub - 1) * n
+        assert weights is None or len(weights) == 16 * n
+        st = (C.c_uint8 * max(1, n))() if want_status else None
+        bad = C.c_uint64(NO_INDEX)
+        rc = self.lib.zkmi_groth16_verify_batch(self.h, vk.h, C.c_uint64(n), _buf(publics), _buf(proofs),
+                                                _buf(weights) if weights is not None else None, st, C.byref(bad))
+        if rc not in (0, -2, -5):
+            self._chk(rc)
+        return rc == 0, (bytes(st)[:n] if want_status else None), (None if bad.value == NO_INDEX else bad.value)
 
     def bases_g1_synthetic_range(self, first, n):
         h = C.c_void_p()

@@ -6,13 +6,15 @@
 // ZkProof::update_account (shielder/mocked_zk/src/relations.rs:79-98).  The
 // algorithm restates ark-groth16 0.4 [not in tree] exactly as oracle/groth16.py
 // does: LibsnarkReduction witness map (3 iNTT, 3 coset NTT, pointwise
-// quotient, 1 coset iNTT), A/B/C assembly with explicit (r, s).
+// quotient, 1 coset iNTT), A/B/C assembly with explicit (r, s).  The device
+// runs six of the seven transforms: c stays in coefficient form and is
+// subtracted after the last inverse transform (k_quotient), same h words.
 //
 // Device pipeline for one proof (all on the ctx stream, key resident in HBM):
 //   upload z (32 B/var) -> to Montgomery
 //   k_matvec x3            a,b,c = <A_i,z>, <B_i,z>, <C_i,z>  (+ input rows)
-//   NTT x7                 see ntt.hip
-//   k_quotient             h = (a*b - c) / Z(g)
+//   NTT x6                 3 iNTT (a, b, c), 2 coset NTT (a, b), 1 coset iNTT; see ntt.hip
+//   k_quotient             a_c * b_c between them; h = (coset-iNTT(a_c b_c) - c) / Z(g) in the last pass
 //   digit-sort(z[1..])     shared by the A, B1, B2 and L MSMs (L query is
 //                          stored padded with n_pub-1 infinities so it lines up)
 //   MSM G1 x3, MSM G2 x1, digit-sort(h), MSM G1 (H)
@@ -171,11 +173,17 @@ k_check_canonical(const uint32_t* __restrict__ z, uint32_t n, uint32_t* __restri
   if (!lt) __hip_atomic_fetch_or(flag, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// a <- a_c * b_c (evaluations on the coset), and in the same launch c <- N c~.  c was never transformed forward: it still
+// holds its coefficients c~_p = c_rev(p) g^rev(p) (bit-reversed order, as the batched inverse left them).  With
+// ab = lo + X^N hi = c + h (X^N - 1), the coset iNTT of a_c * b_c is lo + g^N hi = c + (g^N - 1) h coefficient by
+// coefficient, so the last inverse transform's epilogue gets h_rev(p) = (x_p - N c~_p) * rev_quot_n[p] from its unscaled
+// output x_p (ntt.hpp) -- c's coset NTT and the 1 / Z(g) factor of every evaluation are gone.
 __global__ void __launch_bounds__(256)
-k_quotient(Fr28* __restrict__ a, const Fr28* __restrict__ b, const Fr28* __restrict__ c, Fr28 zinv, uint32_t n) {
+k_quotient(Fr28* __restrict__ a, const Fr28* __restrict__ b, Fr28* __restrict__ c, Fr28 n_field, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  st28(a + i, (ld28(a + i) * ld28(b + i) - ld28(c + i)) * zinv);
+  st28(a + i, ld28(a + i) * ld28(b + i));
+  st28(c + i, ld28(c + i) * n_field);
 }
 
 // the device-resident assignments of a group, gathered back to back: ONE launch of one-wave workgroups instead of one
@@ -929,26 +937,22 @@ static int32_t witness_map_dev(zkmi_ctx* ctx, const zkmi_pk* pk, const void* con
   NttDomain* dom = ctx->domain((int)pk->log_n, &e);
   if (!dom) return ctx->hip_fail(e, "ntt domain");
   if (t) t->begin(PH_NTT, st);
-  // evaluations -> coefficients (bit-reversed, scaled by g^i / N) -> evaluations on the coset
-  // a, b, c together: two batched passes down, two up (3 x G vectors per launch instead of six launch pairs)
+  // evaluations -> coefficients (bit-reversed, scaled by g^i / N) for a, b and c; -> evaluations on the coset for a and b
+  // only (c is needed as coefficients: k_quotient)
+  // a, b, c together: two batched passes down (3 x G vectors per launch), two up (2 x G) instead of launch pairs per vector
   const bool batch_abc = ZK_TUNE("ZKMI_WITNESS_BATCH", 1) != 0;  // A/B library: 0 = one transform per launch
   if (batch_abc) {
     ZK_HIP(ctx, dom->inverse_to_rev(pk->d_a, dom->rev_coset_n, nullptr, st, 3 * G));
-    ZK_HIP(ctx, dom->forward_from_rev(pk->d_a, st, 3 * G));
+    ZK_HIP(ctx, dom->forward_from_rev(pk->d_a, st, 2 * G));
   } else {
     for (int m = 0; m < 3; m++) {
       ZK_HIP(ctx, dom->inverse_to_rev(pk->d_a + (size_t)m * N * G, dom->rev_coset_n, nullptr, st, G));
-      ZK_HIP(ctx, dom->forward_from_rev(pk->d_a + (size_t)m * N * G, st, G));
+      if (m < 2) ZK_HIP(ctx, dom->forward_from_rev(pk->d_a + (size_t)m * N * G, st, G));
     }
   }
-  // 1 / Z(g) with Z(g) = g^N - 1, g = 7
-  Fr gn = fr_from_u64(7);
-  for (uint32_t i = 0; i < pk->log_n; i++) gn = gn.sqr();
-  const Fr zinv = (gn - Fr::one()).inv().from_mont();
-  const Fr28 zinv28 = Fr28::from_canonical(zinv.l);
-  hipLaunchKernelGGL(k_quotient, dim3((G * N + 63) / 64), dim3(64), 0, st, pk->d_a, d_b, d_c, zinv28, G * N);
-  // h coefficients = coset iNTT, left in bit-reversed order as canonical words (H MSM digits)
-  ZK_HIP(ctx, dom->inverse_to_rev(pk->d_a, dom->rev_coset_inv_n, pk->d_h[par], st, G));
+  hipLaunchKernelGGL(k_quotient, dim3((G * N + 63) / 64), dim3(64), 0, st, pk->d_a, d_b, d_c, dom->n_host, G * N);
+  // h coefficients = (coset iNTT of a_c * b_c, minus c) / Z(g), left in bit-reversed order as canonical words (H MSM digits)
+  ZK_HIP(ctx, dom->inverse_to_rev(pk->d_a, dom->rev_quot_n, pk->d_h[par], st, G, d_c));
   if (t) t->end(PH_NTT, st);
   if (st != ctx->stream) ZK_HIP(ctx, hipEventRecord(ctx->ev_h[par], st));
   ZK_HIP(ctx, hipGetLastError());

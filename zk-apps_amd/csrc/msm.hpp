@@ -61,6 +61,10 @@ struct MsmPlan {
   // k_segreduce walks 2^seg_log buckets per thread (a dependent chain of 2 * 2^seg_log additions):
   // 16 buckets when the chip is full anyway, 4 for small problems whose reduction is pure latency
   int seg_log = 4;
+  // second running-sum level of the reduction (msm_impl.hpp k_segreduce2): 2^seg2_log segment sums per super-segment, 0 = none.
+  // NOT part of a sort's plan: MsmEngine::run_device_multi sets it in slot_plan[slot] for the reduction it queues, and the host
+  // combination of that slot's partials reads it there (the partial layout differs: msm_njobs)
+  int seg2_log = 0;
   // batched shared sort (MsmSort::run_shared_batch): nwin = vectors x vec_parts, vector v owns partitions
   // [v * vec_parts, (v + 1) * vec_parts)
   int vec_parts = 1;
@@ -143,6 +147,7 @@ struct MsmEngine {
   XYZZ<F>* buckets = nullptr;  // SLOTS x cap_buckets: one bucket array per MSM in flight
   XYZZ<F>* segsum = nullptr;  // SLOTS x seg_cap: reductions of different slots may run on different streams
   XYZZ<F>* segw = nullptr;
+  XYZZ<F>* seg2 = nullptr;    // SLOTS x 2 x seg_cap / 16: second-level sums of segsum (k_segreduce2: plain, then index-weighted)
   uint64_t seg_cap = 0;
   XYZZ<F>* heavy_partial = nullptr;  // SLOTS x (MSM_HPOOL + MSM_HNC_POOL) partial sums of heavy buckets (msm_impl.hpp)
   uint32_t* heavy_ticket = nullptr;  // SLOTS x MSM_HEAVY_CAP: workgroups of a split heavy bucket that have finished (k_accum_heavy)

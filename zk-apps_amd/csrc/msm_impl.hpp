@@ -25,9 +25,12 @@
 //     k_accum_heavy[_g2_split]  workgroups per heavy bucket (the last one of a split bucket adds the sub-range sums),
 //     k_accum_redo[_g2_split]   buckets that met P + P, with the complete addition
 //   5 k_segreduce thread/2..16 buckets : running-sum  sum (i+1) B_i  and  sum B_i
+//   5b k_segreduce2 (one-lane reductions of shared-bucket plans with >= 256 segments per window): the same running sums
+//                 over 16 consecutive segsum entries -- segsum2 and segt2, see TreeLevel2
 //   6 k_treesum   block/(window, job[, slice]) : plain sums (LDS tree) of segw, and of
 //                 segsum over {t : bit j of t set}; small plans: slices + k_treesum_final
 //   host: window_w = P[w][0] + SEG * sum_j 2^j P[w][1+j];  result = sum_w 2^(c w) window_w
+//         (with 5b: window_w = P[w][0] + SEG * (T[w] + 16 * sum_j 2^j P2[w][1+j]), windows_from_partials)
 #pragma once
 #include <stdlib.h>
 #include <functional>
@@ -41,6 +44,8 @@ namespace zkmi {
 
 // segment arrays: 16-bucket segments for big plans, down to 1-bucket segments for plans of <= 2^16 buckets
 static inline uint64_t msm_max_segments(uint64_t buckets) { return (buckets / 16 > (1u << 16) ? buckets / 16 : (1u << 16)) + 1; }
+constexpr int MSM_SEG2_LOG = 4;             // k_segreduce2: segment sums per super-segment (log2)
+constexpr uint32_t MSM_SEG2_MIN_SEGS = 256;  // ... where a window has at least this many segments
 constexpr int MSM_TREE_T = 128;  // k_treesum block: 128 x XYZZ<Fq2> = 56 KiB LDS
 constexpr uint32_t MSM_STAGE_PTS = 16384;  // slices of one slot's tree-sum job lists (k_treesum_q; the one-lane k_treesum uses the first MSM_STAGE_PTS_1)
 constexpr uint32_t MSM_STAGE_PTS_1 = 4096;
@@ -1168,8 +1173,74 @@ k_segreduce_g2_split(const XYZZ<Fq2_28>* __restrict__ buckets, XYZZ<Fq2_28>* __r
   st_xyzz_split(segw + t, acc, comp);
 }
 
+// Second running-sum level.  The tree sums below weight segment t of a window by t through bit decomposition: every
+// segsum entry is added ~ log2(segments) / 2 times.  With t = 16 u + k,
+//   sum_t t segsum_t = 16 sum_u u segsum2_u + sum_u segt2_u,   segsum2_u = sum_k segsum_(16u+k),  segt2_u = sum_k k segsum_(16u+k),
+// so a thread per super-segment u forms both by the running sums of k_segreduce (31 additions per 16 segments) and the bit
+// jobs walk the 16 x shorter list segsum2; segt2 is one more plain job.  (The plain sum of segw stays what it was: every
+// entry is added once either way.)  The segment lists of the windows lie back to back and are multiples of 16 long, so
+// super-segment u of the array is super-segment u mod (segments / 16) of its window.
+template <class F>
+__global__ void __launch_bounds__(256)
+k_segreduce2(const XYZZ<F>* __restrict__ segsum, XYZZ<F>* __restrict__ segsum2, XYZZ<F>* __restrict__ segt2, uint32_t total_segs2) {
+  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= total_segs2) return;
+  XYZZ<F> run = XYZZ<F>::infinity();
+  XYZZ<F> acc = XYZZ<F>::infinity();
+  for (int k = (1 << MSM_SEG2_LOG) - 1; k >= 0; k--) {
+    XYZZ<F> v = load_vec(segsum + ((size_t)u << MSM_SEG2_LOG) + k);
+    run.add(v);
+    if (k) acc.add(run);  // weight k, not k + 1: segment 0 of a super-segment counts in the plain sum only
+  }
+  store_vec(segsum2 + u, run);
+  store_vec(segt2 + u, acc);
+}
+template <int UNUSED = 0>
+__global__ void __launch_bounds__(256, 2)
+k_segreduce2_g2_split(const XYZZ<Fq2_28>* __restrict__ segsum, XYZZ<Fq2_28>* __restrict__ segsum2, XYZZ<Fq2_28>* __restrict__ segt2,
+                      uint32_t total_segs2) {
+  const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t u = gt >> 1, comp = gt & 1u;
+  if (u >= total_segs2) return;  // pair-uniform
+  XYZZ<Fq2P> run = XYZZ<Fq2P>::infinity();
+  XYZZ<Fq2P> acc = XYZZ<Fq2P>::infinity();
+  for (int k = (1 << MSM_SEG2_LOG) - 1; k >= 0; k--) {
+    XYZZ<Fq2P> v = ld_xyzz_split(segsum + ((size_t)u << MSM_SEG2_LOG) + k, comp);
+    run.add(v);
+    if (k) acc.add(run);
+  }
+  st_xyzz_split(segsum2 + u, run, comp);
+  st_xyzz_split(segt2 + u, acc, comp);
+}
+
+// What the tree-sum kernels read when a second level ran (t_job < 0: none): the bit jobs and the plain job walk segsum2
+// (segs2 entries per window), job t_job is the plain sum of segt2, job 0 stays the plain sum of segw (segs_per_win entries).
+template <class P>
+struct TreeLevel2 {
+  const P* segsum2;
+  const P* segt2;
+  uint32_t segs2;
+  int t_job;
+};
+// the list of (window w, job): first entry, length (whole lists; a bit job enumerates half of that), whole or bit job
+template <class P>
+__device__ __forceinline__ const P* tree_job_list(int job, int w, const P* segsum, const P* segw, uint32_t segs_per_win, int plain_job,
+                                                  const TreeLevel2<P>& l2, uint32_t* len, bool* whole) {
+  *whole = job == 0 || job == plain_job || job == l2.t_job;
+  if (job == 0) {
+    *len = segs_per_win;
+    return segw + (size_t)w * segs_per_win;
+  }
+  if (l2.t_job < 0) {
+    *len = *whole ? segs_per_win : segs_per_win / 2;
+    return segsum + (size_t)w * segs_per_win;
+  }
+  *len = *whole ? l2.segs2 : l2.segs2 / 2;
+  return (job == l2.t_job ? l2.segt2 : l2.segsum2) + (size_t)w * l2.segs2;
+}
+
 // grid = (njobs, nwin, nchunk).  job 0: sum_t segw[w][t]; job j>=1: sum_{t: bit (j-1)} segsum[w][t];
-// job plain_job (shared-bucket mode only): sum_t segsum[w][t].
+// job plain_job (shared-bucket mode only): sum_t segsum[w][t].  With a second level (l2): see TreeLevel2.
 // nchunk = 1: the workgroup sums the job's whole list and writes the result in the host representation.
 // nchunk > 1 (small plans, where the reduction is a latency chain and the chip is empty): workgroup z sums the z-th
 // slice of the list into stage[(w * njobs + job) * nchunk + z]; k_treesum_final adds the slices.  A list of 2^13 segments
@@ -1178,16 +1249,17 @@ template <class F>
 __global__ void __launch_bounds__(MSM_TREE_T)
 k_treesum(const XYZZ<F>* __restrict__ segsum, const XYZZ<F>* __restrict__ segw, uint32_t segs_per_win,
           XYZZ<typename HostFieldOf<F>::type>* __restrict__ partial, int plain_job, XYZZ<F>* __restrict__ stage,
-          XYZZ<typename HostFieldOf<F>::type>* __restrict__ partial_host) {
+          XYZZ<typename HostFieldOf<F>::type>* __restrict__ partial_host, TreeLevel2<XYZZ<F>> l2) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   XYZZ<F>* sh = reinterpret_cast<XYZZ<F>*>(lds_raw);
   const int job = blockIdx.x;
   const int w = blockIdx.y;
   const uint32_t nchunk = gridDim.z, z = blockIdx.z;
-  const XYZZ<F>* src = (job == 0 ? segw : segsum) + (size_t)w * segs_per_win;
-  const bool whole = job == 0 || job == plain_job;
-  const uint32_t len = whole ? segs_per_win : segs_per_win / 2;
+  uint32_t len;
+  bool whole;
+  const XYZZ<F>* src = tree_job_list(job, w, segsum, segw, segs_per_win, plain_job, l2, &len, &whole);
   const uint32_t per = (len + nchunk - 1) / nchunk;
+  // (a list shorter than the slices of job 0 leaves the last slices empty: lo >= hi)
   const uint32_t lo = z * per, hi = lo + per < len ? lo + per : len;
   XYZZ<F> acc = XYZZ<F>::infinity();
   if (whole) {
@@ -1280,16 +1352,17 @@ __device__ __forceinline__ XYZZ<Fq2P> pair_tree_sum(XYZZ<Fq2P> acc, XYZZ<Fq2_28>
 template <int UNUSED = 0>
 __global__ void __launch_bounds__(2 * MSM_TREE_T, 2)
 k_treesum_g2_split(const XYZZ<Fq2_28>* __restrict__ segsum, const XYZZ<Fq2_28>* __restrict__ segw, uint32_t segs_per_win,
-                   XYZZ<Fq2>* __restrict__ partial, int plain_job, XYZZ<Fq2_28>* __restrict__ stage, XYZZ<Fq2>* __restrict__ partial_host) {
+                   XYZZ<Fq2>* __restrict__ partial, int plain_job, XYZZ<Fq2_28>* __restrict__ stage, XYZZ<Fq2>* __restrict__ partial_host,
+                   TreeLevel2<XYZZ<Fq2_28>> l2) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   XYZZ<Fq2_28>* sh = reinterpret_cast<XYZZ<Fq2_28>*>(lds_raw);
   const int job = blockIdx.x;
   const int w = blockIdx.y;
   const uint32_t nchunk = gridDim.z, z = blockIdx.z;
   const uint32_t pair = threadIdx.x >> 1, comp = threadIdx.x & 1u, npair = blockDim.x >> 1;
-  const XYZZ<Fq2_28>* src = (job == 0 ? segw : segsum) + (size_t)w * segs_per_win;
-  const bool whole = job == 0 || job == plain_job;
-  const uint32_t len = whole ? segs_per_win : segs_per_win / 2;
+  uint32_t len;
+  bool whole;
+  const XYZZ<Fq2_28>* src = tree_job_list(job, w, segsum, segw, segs_per_win, plain_job, l2, &len, &whole);
   const uint32_t per = (len + nchunk - 1) / nchunk;
   const uint32_t lo = z * per, hi = lo + per < len ? lo + per : len;
   const uint32_t b = whole ? 0u : (uint32_t)(job - 1), lowmask = (1u << b) - 1u;
@@ -1472,6 +1545,8 @@ void MsmEngine<F>::release() {
   if (buckets) (void)hipFree(buckets);
   if (segsum) (void)hipFree(segsum);
   if (segw) (void)hipFree(segw);
+  if (seg2) (void)hipFree(seg2);
+  seg2 = nullptr;
   if (partial) (void)hipFree(partial);
   if (tree_stage) (void)hipFree(tree_stage);
   tree_stage = nullptr;
@@ -1555,6 +1630,7 @@ hipError_t MsmEngine<F>::reserve(uint64_t n, bool shared_too) {
   seg_cap = msm_max_segments(need);
   if ((e = hipMalloc(&segsum, sizeof(XYZZ<F>) * seg_cap * nslots)) != hipSuccess) return e;
   if ((e = hipMalloc(&segw, sizeof(XYZZ<F>) * seg_cap * nslots)) != hipSuccess) return e;
+  if ((e = hipMalloc(&seg2, sizeof(XYZZ<F>) * 2 * (seg_cap >> MSM_SEG2_LOG) * nslots)) != hipSuccess) return e;
   if ((e = hipMalloc(&partial, sizeof(XYZZ<HF>) * SLOTS * SLOT_PTS)) != hipSuccess) return e;
   if ((e = hipMalloc(&tree_stage, sizeof(XYZZ<F>) * MSM_STAGE_PTS * nslots)) != hipSuccess) return e;
   // per slot: MSM_HPOOL partial sums of split buckets (k_accum_heavy) + MSM_HNC_POOL first-level ones (k_accum_heavy_nc)
@@ -1579,6 +1655,13 @@ static inline int msm_seg_bits(const MsmPlan& pl) {
   int seg_bits = 0;
   while ((1u << seg_bits) < segs_per_win) seg_bits++;
   return seg_bits;
+}
+// partial sums a reduction leaves per window: [0] plain sum of segw, [1 ..] the bit jobs, then (shared-bucket plans) the plain
+// sum of segsum, last.  With a second level (pl.seg2_log, shared plans only): the bit jobs of segsum2, the plain sum of
+// segt2, the plain sum of segsum2.
+static inline int msm_njobs(const MsmPlan& pl) {
+  if (pl.seg2_log) return 3 + msm_seg_bits(pl) - pl.seg2_log;
+  return 1 + msm_seg_bits(pl) + (pl.shared ? 1 : 0);
 }
 
 template <class F>
@@ -1745,8 +1828,12 @@ hipError_t MsmEngine<F>::run_device_multi(const MsmSort* const* sorts, const Aff
       hipLaunchKernelGGL(k_mask_sorted<0>, dim3(1024), dim3(256), 0, st, sorts[m]->sorted, sorts[m]->cap_entries,
                          0x80000000u | ((1u << mask_bits) - 1u));
 #endif
+  // second running-sum level: the one-lane segment and tree sums of shared-bucket plans whose windows have a segment list
+  // long enough for one (the quad / octet kernels, the windowed plans and their exchange layouts keep the single level)
+  const bool level2 = pl.shared && !(quad_mask & 3) && (pl.nb >> pl.seg_log) >= MSM_SEG2_MIN_SEGS;
   for (int m = 0; m < nm; m++) {
     slot_plan[slots[m]] = sorts[m]->plan;
+    slot_plan[slots[m]].seg2_log = level2 ? MSM_SEG2_LOG : 0;
     const hipStream_t st_reduce = st_reduces[m];
     const bool on_reduce = heavy_on == 2 && st_reduce != st;
     const bool side = !on_reduce && heavy_on != 0 && st_heavy && st_heavy != st;
@@ -1911,8 +1998,10 @@ hipError_t MsmEngine<F>::run_device_multi(const MsmSort* const* sorts, const Aff
   const uint32_t segs_per_win = pl.nb >> pl.seg_log;
   const uint32_t tot_segs = pl.nwin * segs_per_win;
   const int seg = 1 << pl.seg_log;
-  const int plain_job = pl.shared ? 1 + msm_seg_bits(pl) : -1;
-  const int njobs = 1 + msm_seg_bits(pl) + (pl.shared ? 1 : 0);
+  const uint32_t segs2 = segs_per_win >> MSM_SEG2_LOG, tot_segs2 = tot_segs >> MSM_SEG2_LOG;  // (level2 only)
+  const int njobs = msm_njobs(slot_plan[slots[0]]);
+  const int plain_job = pl.shared ? njobs - 1 : -1;
+  const int t_job = level2 ? njobs - 2 : -1;
   // small plans: the job lists are cut into slices of two segments per thread or lane pair (k_treesum_final adds the slices)
   constexpr bool is_g2 = std::is_same<F, Fq2_28>::value;
   const uint32_t per_block = is_g2 ? MSM_TREE_T : 2 * MSM_TREE_T;  // G2: 64 lane pairs x 2 segments
@@ -1998,6 +2087,16 @@ hipError_t MsmEngine<F>::run_device_multi(const MsmSort* const* sorts, const Aff
       else
         hipLaunchKernelGGL(k_segreduce<F>, dim3((tot_segs + T - 1) / T), dim3(T), 0, st_reduce, bk, ssum, sw, tot_segs, seg, bk2, bk3);
     }
+    TreeLevel2<XYZZ<F>> l2 = {nullptr, nullptr, 0u, -1};
+    if (level2) {
+      XYZZ<F>* const s2 = seg2 + (size_t)slot * 2 * (seg_cap >> MSM_SEG2_LOG);
+      XYZZ<F>* const t2 = s2 + (seg_cap >> MSM_SEG2_LOG);
+      if constexpr (is_g2)
+        hipLaunchKernelGGL(k_segreduce2_g2_split<0>, dim3((2 * tot_segs2 + T - 1) / T), dim3(T), 0, st_reduce, ssum, s2, t2, tot_segs2);
+      else
+        hipLaunchKernelGGL(k_segreduce2<F>, dim3((tot_segs2 + T - 1) / T), dim3(T), 0, st_reduce, ssum, s2, t2, tot_segs2);
+      l2 = {s2, t2, segs2, t_job};
+    }
     XYZZ<HF>* dp = partial + (size_t)slot * SLOT_PTS;
     XYZZ<HF>* const hp_out = h_partial + (size_t)slot * SLOT_PTS;  // pinned host slot, written by the tree-sum kernels themselves
     XYZZ<F>* const stg = tree_stage + (size_t)slot * MSM_STAGE_PTS;
@@ -2012,7 +2111,7 @@ hipError_t MsmEngine<F>::run_device_multi(const MsmSort* const* sorts, const Aff
     } else if constexpr (is_g2) {
       if (nchunk > 1) {
         hipLaunchKernelGGL(k_treesum_g2_split<0>, dim3(njobs, pl.nwin, nchunk), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T / 2, st_reduce,
-                           ssum, sw, segs_per_win, dp, plain_job, stg, hp_out);
+                           ssum, sw, segs_per_win, dp, plain_job, stg, hp_out, l2);
         uint32_t tf = 64;
         while (tf < 2 * nchunk) tf <<= 1;
         hipLaunchKernelGGL(k_treesum_final_g2_split<0>, dim3(njobs, pl.nwin), dim3(tf), sizeof(XYZZ<F>) * tf / 2, st_reduce, stg, nchunk, dp, hp_out);
@@ -2022,15 +2121,15 @@ hipError_t MsmEngine<F>::run_device_multi(const MsmSort* const* sorts, const Aff
 #ifdef ZKMI_EXPERIMENTS
         if (ZK_TUNE("ZKMI_G2_TREE_SPLIT", 1) == 0)
           hipLaunchKernelGGL(k_treesum<F>, dim3(njobs, pl.nwin, 1), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T, st_reduce,
-                             ssum, sw, segs_per_win, dp, plain_job, stg, hp_out);
+                             ssum, sw, segs_per_win, dp, plain_job, stg, hp_out, l2);
         else
 #endif
           hipLaunchKernelGGL(k_treesum_g2_split<0>, dim3(njobs, pl.nwin, 1), dim3(2 * MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T, st_reduce,
-                             ssum, sw, segs_per_win, dp, plain_job, stg, hp_out);
+                             ssum, sw, segs_per_win, dp, plain_job, stg, hp_out, l2);
       }
     } else {
       hipLaunchKernelGGL(k_treesum<F>, dim3(njobs, pl.nwin, nchunk), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T, st_reduce,
-                         ssum, sw, segs_per_win, dp, plain_job, stg, hp_out);
+                         ssum, sw, segs_per_win, dp, plain_job, stg, hp_out, l2);
       if (nchunk > 1) {
         uint32_t tf = 64;
         while (tf < nchunk) tf <<= 1;
@@ -2056,11 +2155,11 @@ hipError_t MsmEngine<F>::finish_host_windows(XYZZ<HF>* out_windows, int slot) {
 // the per-(window, job) sums a reduction leaves behind -> one sum per window (host arithmetic).  `h` may come from this
 // device's pinned slot or from another rank's copy of the same array (comm.hip: the all-gathered partials of a point split).
 template <class F>
-int MsmEngine<F>::partials_per_msm(const MsmPlan& pl) { return pl.nwin * (1 + msm_seg_bits(pl) + (pl.shared ? 1 : 0)); }
+int MsmEngine<F>::partials_per_msm(const MsmPlan& pl) { return pl.nwin * msm_njobs(pl); }
 template <class F>
 void MsmEngine<F>::windows_from_partials(const MsmPlan& pl, const XYZZ<HF>* h, XYZZ<HF>* out_windows, bool parallel) {
-  const int seg_bits = msm_seg_bits(pl);
-  const int njobs = 1 + seg_bits + (pl.shared ? 1 : 0);
+  const int seg_bits = msm_seg_bits(pl) - pl.seg2_log;  // bit jobs: over the segments, or over the second level's super-segments
+  const int njobs = msm_njobs(pl);
   const std::function<void(uint32_t)> one = [&](uint32_t w) {
     XYZZ<HF> u = XYZZ<HF>::infinity();
     // (top window of a partitioned big-window plan: the top bits of the segment index number the partition its entries
@@ -2069,6 +2168,11 @@ void MsmEngine<F>::windows_from_partials(const MsmPlan& pl, const XYZZ<HF>* h, X
     for (int j = bits - 1; j >= 0; j--) {
       u.dbl_inplace();
       u.add(h[(size_t)w * njobs + 1 + j]);
+    }
+    if (pl.seg2_log) {
+      // sum_t t segsum_t = 2^seg2_log sum_u u segsum2_u + sum_u segt2_u (k_segreduce2)
+      for (int i = 0; i < pl.seg2_log; i++) u.dbl_inplace();
+      u.add(h[(size_t)w * njobs + njobs - 2]);
     }
     for (int i = 0; i < pl.seg_log; i++) u.dbl_inplace();
     u.add(h[(size_t)w * njobs]);
@@ -2106,7 +2210,7 @@ hipError_t MsmEngine<F>::finish_host_batch(XYZZ<HF>* out, int slot) {
   std::vector<XYZZ<HF>> win(pl.nwin);
   hipError_t e = finish_host_windows(win.data(), slot);
   if (e != hipSuccess) return e;
-  const int njobs = 2 + msm_seg_bits(pl);
+  const int njobs = msm_njobs(pl);
   const XYZZ<HF>* h = h_partial + (size_t)slot * SLOT_PTS;
   for (int v = 0; v * pl.vec_parts < pl.nwin; v++)
     out[v] = msm_combine_partitions<HF>(win.data() + (size_t)v * pl.vec_parts, h + (size_t)v * pl.vec_parts * njobs, pl.vec_parts,
@@ -2122,7 +2226,7 @@ template <class F>
 XYZZ<typename MsmEngine<F>::HF> MsmEngine<F>::host_result_vec(int slot, int v) const {
   const MsmPlan& pl = slot_plan[slot];
   const int vp = pl.vec_parts > 1 ? pl.vec_parts : 1;
-  const int njobs = 1 + msm_seg_bits(pl) + (pl.shared ? 1 : 0);
+  const int njobs = msm_njobs(pl);
   const XYZZ<HF>* h = h_partial + (size_t)slot * SLOT_PTS + (size_t)v * vp * njobs;
   MsmPlan mine = pl;  // the partitions of this vector only
   mine.nwin = vp;
@@ -2152,7 +2256,7 @@ hipError_t MsmEngine<F>::finish_host(XYZZ<HF>* out, int slot) {
     *out = msm_combine_windows(win.data(), pl.nwin, pl.c);
     return hipSuccess;
   }
-  *out = msm_combine_partitions<HF>(win.data(), h_partial + (size_t)slot * SLOT_PTS, pl.nwin, 2 + msm_seg_bits(pl), pl.nb);
+  *out = msm_combine_partitions<HF>(win.data(), h_partial + (size_t)slot * SLOT_PTS, pl.nwin, msm_njobs(pl), pl.nb);
   return hipSuccess;
 }
 

@@ -57,14 +57,16 @@ __global__ void k_bitrev_copy(const F* __restrict__ in, F* __restrict__ out, int
 // the two-pass split are applied once per element ("twist") — at the load of the strided
 // DIT pass, at the store of the strided DIF pass — instead of one global twiddle gather
 // per butterfly.  Without LOCAL_TW (three passes, N > 2^20) twiddles are gathered per butterfly.
-// post (optional): every output is multiplied by post[position].  canon_out (optional):
+// post (optional): every output is multiplied by post[position].  sub (optional, with post; laid out like data): the
+// output is (x - sub[position]) * post[position] -- the witness map's quotient fix-up.  canon_out (optional):
 // outputs are written as canonical 32-byte integers instead of limbs (H MSM digits).
 template <class F, bool DIF, bool LOCAL_TW, int THREADS>
 __global__ void __launch_bounds__(THREADS)
 k_ntt_pass(F* __restrict__ data, const F* __restrict__ tw, int log_n, int t0, int S, int Q,
-           const F* __restrict__ post, uint32_t* __restrict__ canon_out) {
-  // blockIdx.y = transform of a batch: vectors of 2^log_n elements laid out back to back (same for canon_out)
+           const F* __restrict__ post, const F* __restrict__ sub, uint32_t* __restrict__ canon_out) {
+  // blockIdx.y = transform of a batch: vectors of 2^log_n elements laid out back to back (same for sub and canon_out)
   data += (size_t)blockIdx.y << log_n;
+  if (sub) sub += (size_t)blockIdx.y << log_n;
   if (canon_out) canon_out += ((size_t)blockIdx.y << log_n) * 8;
   extern __shared__ __align__(16) unsigned char lds_raw[];
   F* tile = reinterpret_cast<F*>(lds_raw);
@@ -137,6 +139,7 @@ k_ntt_pass(F* __restrict__ data, const F* __restrict__ tw, int log_n, int t0, in
     const uint32_t g = gindex(L);
     F v = tile[L];
     if (LOCAL_TW && DIF && t0 > 0) v = v * twist(L);
+    if (sub) v = v - ld28(sub + g);
     if (post) v = v * ld28(post + g);
     if (canon_out) {
       uint32_t w[8];
@@ -157,6 +160,13 @@ __global__ void __launch_bounds__(256)
 k_mul_table(F* __restrict__ a, const F* __restrict__ b, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) st28(a + i, ld28(a + i) * ld28(b + i));
+}
+
+template <class F>
+__global__ void __launch_bounds__(256)
+k_sub(F* __restrict__ a, const F* __restrict__ b, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) st28(a + i, ld28(a + i) - ld28(b + i));
 }
 
 template <class F>
@@ -244,7 +254,7 @@ static F to28(const H& a) {
 
 template <class F>
 NttDomainT<F>::~NttDomainT() {
-  F* ptrs[] = {tw_fwd, tw_inv, coset_fwd, coset_inv_n, rev_coset_n, rev_coset_inv_n, n_inv, scratch};
+  F* ptrs[] = {tw_fwd, tw_inv, coset_fwd, coset_inv_n, rev_coset_n, rev_quot_n, n_inv, scratch};
   for (F* p : ptrs)
     if (p) (void)hipFree(p);
 }
@@ -257,7 +267,7 @@ hipError_t NttDomainT<F>::init(int log_n_, hipStream_t stream) {
   const uint32_t n = 1u << log_n;
   const uint32_t half = n > 1 ? n / 2 : 1;
   hipError_t e;
-  F** alloc_n[] = {&coset_fwd, &coset_inv_n, &rev_coset_n, &rev_coset_inv_n, &scratch};
+  F** alloc_n[] = {&coset_fwd, &coset_inv_n, &rev_coset_n, &rev_quot_n, &scratch};
   if ((e = hipMalloc(&tw_fwd, sizeof(F) * half)) != hipSuccess) return e;
   if ((e = hipMalloc(&tw_inv, sizeof(F) * half)) != hipSuccess) return e;
   if ((e = hipMalloc(&n_inv, sizeof(F))) != hipSuccess) return e;
@@ -278,7 +288,13 @@ hipError_t NttDomainT<F>::init(int log_n_, hipStream_t stream) {
   // position-indexed tables for bit-reversed coefficient order: entry p <- index rev(p)
   hipLaunchKernelGGL(k_power_table<F>, dim3(blocks(n)), dim3(T), 0, stream, scratch, to28<F, H>(g), ninv28, n);
   hipLaunchKernelGGL(k_bitrev_copy<F>, dim3((n + T - 1) / T), dim3(T), 0, stream, scratch, rev_coset_n, log_n);
-  hipLaunchKernelGGL(k_bitrev_copy<F>, dim3((n + T - 1) / T), dim3(T), 0, stream, coset_inv_n, rev_coset_inv_n, log_n);
+  // the quotient table: 1 / (N Z(g)) g^-rev(p) with Z(g) = g^N - 1, the vanishing polynomial's value on the coset
+  H gn = g;
+  for (int i = 0; i < log_n; i++) gn = gn.sqr();
+  const H zinv = (gn - H::one()).inv();
+  n_host = to28<F, H>(host_from_u64<H>(n));
+  hipLaunchKernelGGL(k_power_table<F>, dim3(blocks(n)), dim3(T), 0, stream, scratch, to28<F, H>(g.inv()), to28<F, H>(ninv * zinv), n);
+  hipLaunchKernelGGL(k_bitrev_copy<F>, dim3((n + T - 1) / T), dim3(T), 0, stream, scratch, rev_quot_n, log_n);
   if ((e = hipMemcpyAsync(n_inv, &ninv28, sizeof(F), hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
   return hipGetLastError();
@@ -305,16 +321,16 @@ static int ntt_rb_mode() { return ZK_TUNE("ZKMI_NTT_RB", 6); }
 #ifdef ZKMI_EXPERIMENTS
 template <class F, bool DIF, bool LTW, int LOGE, int LOGR = 0, bool ONEW = false>
 static void launch_rb(dim3 grid, uint32_t tile_n, int S, hipStream_t stream, F* buf, const F* tw, int log_n, int t0, int Q,
-                      const F* post, uint32_t* canon_out) {
+                      const F* post, const F* sub, uint32_t* canon_out) {
   const size_t words = (size_t)F::NL * (tile_n + (tile_n >> 5)) +
                        (LTW ? (size_t)F::NL * ((1u << (S - 1)) + ((1u << (S - 1)) >> 5) + 1u) : 0u);
   hipLaunchKernelGGL((k_ntt_pass_rb<F, DIF, LTW, LOGE, LOGR, ONEW>), grid, dim3(tile_n >> (LOGE + LOGR)), words * sizeof(uint32_t), stream,
-                     buf, tw, log_n, t0, S, Q, post, canon_out);
+                     buf, tw, log_n, t0, S, Q, post, sub, canon_out);
 }
 #endif
 
 template <class F, bool DIF>
-static hipError_t run_passes(F* buf, const F* tw, int log_n, const F* post, uint32_t* canon_out,
+static hipError_t run_passes(F* buf, const F* tw, int log_n, const F* post, const F* sub, uint32_t* canon_out,
                              hipStream_t stream, uint32_t batch = 1) {
   const uint32_t n = 1u << log_n;
   int mode = ntt_rb_mode();
@@ -367,25 +383,26 @@ static hipError_t run_passes(F* buf, const F* tw, int log_n, const F* post, uint
     const uint32_t tile_n = 1u << (p.S + p.Q);
     const uint32_t nblk = n / tile_n;
     const F* pp = last ? post : nullptr;
+    const F* sb = last ? sub : nullptr;
     uint32_t* co = last ? canon_out : nullptr;
     const dim3 grid(nblk, batch);
 #ifdef ZKMI_EXPERIMENTS
     if (rb == 5) {  // tile_n == 512 by construction (log_n >= 9)
-      launch_rb<F, DIF, true, 2, 1, true>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, co);  // 4 elements x 2 units per thread
+      launch_rb<F, DIF, true, 2, 1, true>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, sb, co);  // 4 elements x 2 units per thread
       continue;
     }
     if (rb == 4 && tile_n == 1024) {
-      if (local_tw) launch_rb<F, DIF, true, 2, 2>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, co);
-      else launch_rb<F, DIF, false, 2, 2>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, co);
+      if (local_tw) launch_rb<F, DIF, true, 2, 2>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, sb, co);
+      else launch_rb<F, DIF, false, 2, 2>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, sb, co);
       continue;
     }
     if (rb && rb != 4 && rb != 5 && tile_n >= 512) {
       if (rb == 2) {
-        if (local_tw) launch_rb<F, DIF, true, 2>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, co);
-        else launch_rb<F, DIF, false, 2>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, co);
+        if (local_tw) launch_rb<F, DIF, true, 2>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, sb, co);
+        else launch_rb<F, DIF, false, 2>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, sb, co);
       } else {
-        if (local_tw) launch_rb<F, DIF, true, 3>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, co);
-        else launch_rb<F, DIF, false, 3>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, co);
+        if (local_tw) launch_rb<F, DIF, true, 3>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, sb, co);
+        else launch_rb<F, DIF, false, 3>(grid, tile_n, p.S, stream, buf, tw, log_n, p.t0, p.Q, pp, sb, co);
       }
       continue;
     }
@@ -393,43 +410,46 @@ static hipError_t run_passes(F* buf, const F* tw, int log_n, const F* post, uint
     const size_t lds = ((size_t)tile_n + (local_tw ? (1u << (p.S - 1)) : 0u)) * sizeof(F);
     if (tile_n == 1024 && mode == 6) {
       if (local_tw)
-        hipLaunchKernelGGL((k_ntt_pass<F, DIF, true, 512>), grid, dim3(512), lds, stream, buf, tw, log_n, p.t0, p.S, p.Q, pp, co);
+        hipLaunchKernelGGL((k_ntt_pass<F, DIF, true, 512>), grid, dim3(512), lds, stream, buf, tw, log_n, p.t0, p.S, p.Q, pp, sb, co);
       else
-        hipLaunchKernelGGL((k_ntt_pass<F, DIF, false, 512>), grid, dim3(512), lds, stream, buf, tw, log_n, p.t0, p.S, p.Q, pp, co);
+        hipLaunchKernelGGL((k_ntt_pass<F, DIF, false, 512>), grid, dim3(512), lds, stream, buf, tw, log_n, p.t0, p.S, p.Q, pp, sb, co);
     } else if (tile_n >= 1024) {
       if (local_tw)
         hipLaunchKernelGGL((k_ntt_pass<F, DIF, true, 1024>), grid, dim3(1024), lds, stream, buf, tw, log_n, p.t0, p.S,
-                           p.Q, pp, co);
+                           p.Q, pp, sb, co);
       else
         hipLaunchKernelGGL((k_ntt_pass<F, DIF, false, 1024>), grid, dim3(1024), lds, stream, buf, tw, log_n, p.t0,
-                           p.S, p.Q, pp, co);
+                           p.S, p.Q, pp, sb, co);
     } else if (local_tw) {
       hipLaunchKernelGGL((k_ntt_pass<F, DIF, true, 64>), grid, dim3(64), lds, stream, buf, tw, log_n, p.t0, p.S, p.Q,
-                         pp, co);
+                         pp, sb, co);
     } else {
       hipLaunchKernelGGL((k_ntt_pass<F, DIF, false, 64>), grid, dim3(64), lds, stream, buf, tw, log_n, p.t0, p.S, p.Q,
-                         pp, co);
+                         pp, sb, co);
     }
   }
   return hipGetLastError();
 }
 
 template <class F>
-hipError_t NttDomainT<F>::inverse_to_rev(F* d, const F* post_table, uint32_t* canon_out, hipStream_t st, uint32_t batch) {
+hipError_t NttDomainT<F>::inverse_to_rev(F* d, const F* post_table, uint32_t* canon_out, hipStream_t st, uint32_t batch,
+                                         const F* sub) {
+  if (sub && !post_table) return hipErrorInvalidValue;
   if (log_n == 0) {
     if (batch != 1) return hipErrorInvalidValue;
-    // single element: only the post factor / output format applies
+    // single element: only the subtrahend / post factor / output format applies
+    if (sub) hipLaunchKernelGGL(k_sub<F>, dim3(1), dim3(256), 0, st, d, sub, 1u);
     if (post_table) hipLaunchKernelGGL(k_mul_table<F>, dim3(1), dim3(256), 0, st, d, post_table, 1u);
     if (canon_out) hipLaunchKernelGGL(k_to_canonical<F>, dim3(1), dim3(256), 0, st, d, canon_out, 1u);
     return hipGetLastError();
   }
-  return run_passes<F, true>(d, tw_inv, log_n, post_table, canon_out, st, batch);
+  return run_passes<F, true>(d, tw_inv, log_n, post_table, sub, canon_out, st, batch);
 }
 
 template <class F>
 hipError_t NttDomainT<F>::forward_from_rev(F* d, hipStream_t st, uint32_t batch) {
   if (log_n == 0) return hipSuccess;
-  return run_passes<F, false>(d, tw_fwd, log_n, nullptr, nullptr, st, batch);
+  return run_passes<F, false>(d, tw_fwd, log_n, nullptr, nullptr, nullptr, st, batch);
 }
 
 // natural order in and out (public entry point)
@@ -441,7 +461,7 @@ hipError_t NttDomainT<F>::transform(F* d_data, bool inverse, bool coset, hipStre
     hipLaunchKernelGGL(k_mul_table<F>, dim3((n + T - 1) / T), dim3(T), 0, stream, d_data, coset_fwd, n);
   if (log_n > 0) {
     hipLaunchKernelGGL(k_bitrev_copy<F>, dim3((n + T - 1) / T), dim3(T), 0, stream, d_data, scratch, log_n);
-    hipError_t e = run_passes<F, false>(scratch, inverse ? tw_inv : tw_fwd, log_n, nullptr, nullptr, stream);
+    hipError_t e = run_passes<F, false>(scratch, inverse ? tw_inv : tw_fwd, log_n, nullptr, nullptr, nullptr, stream);
     if (e != hipSuccess) return e;
     if ((e = hipMemcpyAsync(d_data, scratch, sizeof(F) * n, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
   }

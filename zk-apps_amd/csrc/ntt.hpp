@@ -46,20 +46,24 @@ struct NttDomainT {
   F* coset_fwd = nullptr;        // g^i            (natural order, g = 7)
   F* coset_inv_n = nullptr;      // N^-1 g^-i      (natural order)
   F* rev_coset_n = nullptr;      // N^-1 g^rev(p)  (position-indexed, bit-reversed coefficients)
-  F* rev_coset_inv_n = nullptr;  // N^-1 g^-rev(p)
+  F* rev_quot_n = nullptr;       // N^-1 g^-rev(p) / (g^N - 1): coset iNTT post factor with the quotient's 1/Z(g) folded in
   F* n_inv = nullptr;            // N^-1
   F* scratch = nullptr;          // N elements
   F n_inv_host;
+  F n_host;                      // N
   ~NttDomainT();
   hipError_t init(int log_n, hipStream_t stream);
   // natural order in and out (public entry point)
   hipError_t transform(F* d_data, bool inverse, bool coset, hipStream_t stream);
   // prover building blocks, no bit-reversal copies:
   //   inverse_to_rev : evaluations (natural) -> coefficients in bit-reversed order, each
-  //                    multiplied by post_table[position]; optionally written as canonical words
+  //                    multiplied by post_table[position]; optionally written as canonical words.
+  //                    sub (optional, needs post_table; batch vectors back to back like d): each output is
+  //                    (x - sub[position]) * post_table[position] instead
   //   forward_from_rev: coefficients in bit-reversed order -> evaluations (natural)
   // batch > 1: `batch` vectors of 2^log_n elements back to back in d (and in canon_out), one launch per pass
-  hipError_t inverse_to_rev(F* d, const F* post_table, uint32_t* canon_out, hipStream_t st, uint32_t batch = 1);
+  hipError_t inverse_to_rev(F* d, const F* post_table, uint32_t* canon_out, hipStream_t st, uint32_t batch = 1,
+                            const F* sub = nullptr);
   hipError_t forward_from_rev(F* d, hipStream_t st, uint32_t batch = 1);
 };
 

@@ -53,10 +53,11 @@ struct RbLds {
 template <class F, bool DIF, bool LOCAL_TW, int LOGE, int LOGR = 0, bool ONEW = false>
 __global__ void __launch_bounds__((LOGR || ONEW) ? 64 : (2048 >> LOGE), ONEW ? 3 : 1)
 k_ntt_pass_rb(F* __restrict__ data, const F* __restrict__ tw, int log_n, int t0, int S, int Q,
-              const F* __restrict__ post, uint32_t* __restrict__ canon_out) {
+              const F* __restrict__ post, const F* __restrict__ sub, uint32_t* __restrict__ canon_out) {
   constexpr int E = 1 << LOGE;
   constexpr int REP = 1 << LOGR;
   data += (size_t)blockIdx.y << log_n;
+  if (sub) sub += (size_t)blockIdx.y << log_n;
   if (canon_out) canon_out += ((size_t)blockIdx.y << log_n) * 8;
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const uint32_t tile_n = 1u << (S + Q);
@@ -165,6 +166,7 @@ k_ntt_pass_rb(F* __restrict__ data, const F* __restrict__ tw, int log_n, int t0,
     const uint32_t g = gindex(L);
     F v = tile.ld(L);
     if (LOCAL_TW && DIF && t0 > 0) v = v * twist(L);
+    if (sub) v = v - ld28(sub + g);
     if (post) v = v * ld28(post + g);
     if (canon_out) {
       uint32_t w[8];

@@ -85,6 +85,31 @@ def check_msms(zk, ctx, ocpp, group, n, kinds=KINDS):
     b.free()
 
 
+def check_degenerate_msms(ctx, group):
+    """The point and scalar patterns of test_gpu_parity.py::test_msm_degenerate_bases_and_scalars at reps 1 (9 points: P + P in
+    a light bucket, so the redo pass runs with a non-empty list; P - P; infinity) and 400 (3 600 points per bucket: the heavy
+    kernels), against the same closed form over oracle/bls12_381.py."""
+    F, G = (ec.Fq, ec.G1) if group == 1 else (ec.Fq2, ec.G2)
+    mul = ec.g1_mul if group == 1 else ec.g2_mul
+    to_b = ec.g1_to_bytes if group == 1 else ec.g2_to_bytes
+    width = 96 if group == 1 else 192
+    neg = lambda p: ec.pt_neg(F, p)
+    P2, P3 = mul(2), mul(3)
+    pts = [G, G, neg(G), G, None, P2, neg(P2), P3, P3]
+    k = 0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890AB % R
+    for reps, sc in ((1, [k] * 9), (1, [k, k, k, R - 1, 5, 0, 1, R - 1, R - 1]), (400, [k] * 9)):
+        want = None
+        for s, p in zip(sc, pts):
+            if p is not None and s:
+                want = ec.pt_add(F, want, ec.pt_mul(F, p, s))
+        want = ec.pt_mul(F, want, reps) if want is not None else None
+        raw_b = b"".join(to_b(p) if p is not None else bytes(width) for p in pts * reps)
+        b = ctx.bases_g1(raw_b) if group == 1 else ctx.bases_g2(raw_b)
+        got = (ctx.msm_g1 if group == 1 else ctx.msm_g2)(frs(sc * reps), b)
+        assert got == (to_b(want) if want is not None else bytes(width)), (group, reps, sc[:4])
+        b.free()
+
+
 @pytest.fixture(scope="module")
 def ocpp():
     from oracle import cpp
@@ -101,11 +126,15 @@ def test_prepared_msm_on_both_sides_of_the_threshold_vs_cpp_oracle(ctx, zk, ocpp
 
 def test_prepared_msm_through_the_one_lane_reduction_vs_cpp_oracle(zk):
     """The same cases in a child process over the A/B library with ZKMI_QUAD = ZKMI_QUAD_G2 = 0: a single MSM then reduces
-    with k_segreduce / k_treesum (G2: the lane-pair forms) and, above the threshold, with the second level."""
+    with k_segreduce / k_treesum (G2: the lane-pair forms) and, above the threshold, with the second level.  The child also
+    feeds the one-lane and lane-pair k_accum_redo and k_accum_heavy a redo list that is not empty and heavy buckets
+    (check_degenerate_msms); a second child adds ZKMI_HEAVY_NC=0, the point mode of k_accum_heavy."""
     assert os.path.exists(EXP_LIB), "zk-apps_amd/libzkmi_exp.so missing: run __graft_entry__.build() (make experiments)"
-    env = dict(os.environ, ZKMI_LIB=EXP_LIB, ZKMI_QUAD="0", ZKMI_QUAD_G2="0")
-    p = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
-    assert p.returncode == 0 and "ONE_LANE_MSMS_OK" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
+    for extra in ({}, {"ZKMI_HEAVY_NC": "0"}):
+        env = dict(os.environ, ZKMI_LIB=EXP_LIB, ZKMI_QUAD="0", ZKMI_QUAD_G2="0", **extra)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+        assert p.returncode == 0 and "ONE_LANE_MSMS_OK" in p.stdout and "DEGENERATE_MSMS_OK" in p.stdout, (
+            extra, p.stdout[-1500:], p.stderr[-3000:])
 
 
 def test_group_of_three_proofs_with_a_second_level_fold_and_no_fold_vs_cpp_oracle(ctx, zk, ocpp):
@@ -165,5 +194,8 @@ if __name__ == "__main__":
     for grp in (1, 2):
         for size in sizes.values():
             check_msms(z, c, cpp, grp, size)
-    c.close()
     print("ONE_LANE_MSMS_OK", sizes)
+    for grp in (1, 2):
+        check_degenerate_msms(c, grp)
+    print("DEGENERATE_MSMS_OK")
+    c.close()

@@ -29,6 +29,8 @@
 //                 over 16 consecutive segsum entries -- segsum2 and segt2, see TreeLevel2
 //   6 k_treesum   block/(window, job[, slice]) : plain sums (LDS tree) of segw, and of
 //                 segsum over {t : bit j of t set}; small plans: slices + k_treesum_final
+//   Steps 5 - 6 and the two k_accum_* lines of step 4 have ONE body per algorithm, over a lane layout (OneLane<F>: a lane per
+//   point; LanePair: a G2 point across a lane pair, the _g2_split entry points): see "Lane layouts" below.
 //   host: window_w = P[w][0] + SEG * sum_j 2^j P[w][1+j];  result = sum_w 2^(c w) window_w
 //         (with 5b: window_w = P[w][0] + SEG * (T[w] + 16 * sum_j 2^j P2[w][1+j]), windows_from_partials)
 #pragma once
@@ -597,39 +599,137 @@ k_accum_g2_split2(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Lane layouts of the reduction-side kernels (redo, heavy buckets, segment sums, tree sums).  Each of these algorithms has
+// ONE body, written over a layout L that says how a point lies across lanes; the __global__ entry points behind each body
+// are one call each and differ in layout and __launch_bounds__ only.
+//   OneLane<F>  a lane per point (G1, BN254 G1; the unsplit G2 tree sum of the A/B library)
+//   LanePair    a lane pair per G2 point, one Fq2 component per lane (field28.hpp Fq2P, see k_accum_g2_nc): per-lane state
+//               is that of a G1 addition.  The unsplit forms are 330-register kernels with 45-75 us per dependent addition:
+//               0.8 ms for one 600-point bucket of a 2^14 proof, on the critical path of the G2 reduction; and 0.1 ms to
+//               place an EMPTY redo kernel.
+// Memory layouts are the unsplit ones for both.  Thread i (of the workgroup, or of the grid) is lane `comp` = i % LANES of
+// point i / LANES, and every branch around an addition is uniform over the lanes of a point.
+// ---------------------------------------------------------------------------------------------
+template <class F>
+struct OneLane {
+  typedef XYZZ<F> Stored;                             // the point in memory
+  typedef XYZZ<F> P;                                  // what a lane holds of it
+  typedef XYZZ<typename HostFieldOf<F>::type> Host;   // the host-representation point
+  typedef Affine<F> Base;                             // a table entry in memory
+  static constexpr uint32_t LANES = 1;
+  __device__ __forceinline__ static P load(const Stored* p, uint32_t) { return load_vec(p); }
+  __device__ __forceinline__ static void store(Stored* p, const P& v, uint32_t) { store_vec(p, v); }
+  __device__ __forceinline__ static void store_host(Host* p, const P& v, uint32_t) {
+    const Host o = {fq_from_fq28(v.x), fq_from_fq28(v.y), fq_from_fq28(v.zz), fq_from_fq28(v.zzz)};
+    store_vec(p, o);
+  }
+  // the table entry of a sorted[] word, negated where the word's sign bit is set
+  __device__ __forceinline__ static Affine<F> load_affine(const Base* bases, uint32_t v, uint32_t) {
+    Affine<F> p = load_vec(bases + (v & 0x7fffffffu));
+    if (v >> 31) p.y = p.y.neg();
+    return p;
+  }
+  // heavy_marker() left by k_accum_heavy_nc: "infinity" with zzz word 0 set; *empty: all zz words zero, marker or not
+  __device__ __forceinline__ static bool is_marker(const P& v, uint32_t, bool* empty) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < F::NL; i++) o |= (uint32_t)v.zz.l[i];
+    *empty = o == 0;
+    return o == 0 && v.zzz.l[0] == 1;
+  }
+};
+struct LanePair {
+  typedef XYZZ<Fq2_28> Stored;  // x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1: lane `comp` reads / writes every second one
+  typedef XYZZ<Fq2P> P;
+  typedef XYZZ<Fq2> Host;
+  typedef Affine<Fq2_28> Base;
+  static constexpr uint32_t LANES = 2;
+  __device__ __forceinline__ static P load(const Stored* p, uint32_t comp) {
+    const Fq28* s = reinterpret_cast<const Fq28*>(p);
+    P r;
+    r.x.v = ld_comp(s + comp);
+    r.y.v = ld_comp(s + 2 + comp);
+    r.zz.v = ld_comp(s + 4 + comp);
+    r.zzz.v = ld_comp(s + 6 + comp);
+    return r;
+  }
+  __device__ __forceinline__ static void store(Stored* p, const P& v, uint32_t comp) {
+    Fq28* d = reinterpret_cast<Fq28*>(p);
+    st_comp(d + comp, v.x.v);
+    st_comp(d + 2 + comp, v.y.v);
+    st_comp(d + 4 + comp, v.zz.v);
+    st_comp(d + 6 + comp, v.zzz.v);
+  }
+  __device__ __forceinline__ static void store_host(Host* p, const P& v, uint32_t comp) {
+    Fq* d = reinterpret_cast<Fq*>(p);
+    d[comp] = fq_from_fq28(v.x.v);
+    d[2 + comp] = fq_from_fq28(v.y.v);
+    d[4 + comp] = fq_from_fq28(v.zz.v);
+    d[6 + comp] = fq_from_fq28(v.zzz.v);
+  }
+  __device__ __forceinline__ static Affine<Fq2P> load_affine(const Base* bases, uint32_t v, uint32_t comp) {
+    const Fq28* src = reinterpret_cast<const Fq28*>(bases + (v & 0x7fffffffu));  // x.c0 x.c1 y.c0 y.c1
+    Affine<Fq2P> p;
+    p.x.v = ld_comp(src + comp);
+    p.y.v = ld_comp(src + 2 + comp);
+    if (v >> 31) p.y = p.y.neg();
+    return p;
+  }
+  // the marker of k_accum_heavy_nc_g2 is zzz.c0 word 0: both tests ORed over the pair with one DPP swap each
+  __device__ __forceinline__ static bool is_marker(const P& v, uint32_t comp, bool* empty) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < Fq28::NL; i++) o |= (uint32_t)v.zz.v.l[i];
+    uint32_t mk = (comp == 0 && v.zzz.v.l[0] == 1) ? 1u : 0u;
+    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
+    mk |= (uint32_t)__builtin_amdgcn_mov_dpp((int)mk, 0xB1, 0xF, 0xF, true);
+    *empty = o == 0;
+    return o == 0 && mk == 1;
+  }
+};
+// LDS tree over the npt points a workgroup holds (a power of two; sh: npt x Stored): the sum ends in the lanes of point 0
+template <class L>
+__device__ __forceinline__ typename L::P lanes_tree_sum(typename L::P acc, typename L::Stored* sh, uint32_t pt, uint32_t npt, uint32_t comp) {
+  L::store(sh + pt, acc, comp);
+  __syncthreads();
+  for (uint32_t s = npt / 2; s > 0; s >>= 1) {
+    if (pt < s) {
+      acc.add(L::load(sh + pt + s, comp));
+      L::store(sh + pt, acc, comp);
+    }
+    __syncthreads();
+  }
+  return acc;
+}
+
 // the listed buckets again, with the complete addition (rare: repeated bases with equal digits)
 // The kernel also CLEARS the list for the slot's next MSM: every workgroup reads the length first, and the last one to
 // finish (a ticket word behind the list) resets length and ticket -- no hipMemsetAsync launch in front of an accumulation
 // (a kernel of its own that waited up to 0.8 ms for a slot on a full chip).  The buffer is zeroed once when it is allocated.
-// Round 5: one WAVE per listed bucket (lane l adds entries l, l + 64, ...; LDS tree of the 64 partial sums) instead of one
-// lane: the synthetic bases of the benchmarks and tests, P_i = G + i Q, meet P + P by arithmetic coincidence (a running sum
-// P_a - P_b + P_c IS P_(a - b + c)) about once per 10^7 insertions, and the one lane that then walked its bucket's ~32
-// entries with 16 us per dependent addition held the whole reduction back by 0.2 - 0.5 ms per MSM.
-template <class F>
-__device__ __forceinline__ XYZZ<F> block_tree_sum(XYZZ<F> acc, XYZZ<F>* sh);
-template <class F>
-__global__ void __launch_bounds__(64)
-k_accum_redo(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ begin,
-             const uint32_t* __restrict__ count, const uint32_t* __restrict__ sorted,
-             XYZZ<F>* __restrict__ buckets, uint32_t* __restrict__ redo, uint32_t* __restrict__ ticket, uint32_t into) {
+// Round 5: one WAVE per listed bucket (point l of its 64 / LANES adds entries l, l + 64 / LANES, ...; LDS tree of the partial
+// sums) instead of one lane: the synthetic bases of the benchmarks and tests, P_i = G + i Q, meet P + P by arithmetic
+// coincidence (a running sum P_a - P_b + P_c IS P_(a - b + c)) about once per 10^7 insertions, and the one lane that then
+// walked its bucket's ~32 entries with 16 us per dependent addition held the whole reduction back by 0.2 - 0.5 ms per MSM.
+template <class L>
+__device__ __forceinline__ void accum_redo_body(const typename L::Base* __restrict__ bases, const uint32_t* __restrict__ begin,
+                                                const uint32_t* __restrict__ count, const uint32_t* __restrict__ sorted,
+                                                typename L::Stored* __restrict__ buckets, uint32_t* __restrict__ redo,
+                                                uint32_t* __restrict__ ticket, uint32_t into) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  XYZZ<F>* sh = reinterpret_cast<XYZZ<F>*>(lds_raw);
+  typename L::Stored* sh = reinterpret_cast<typename L::Stored*>(lds_raw);
+  const uint32_t pt = threadIdx.x / L::LANES, comp = threadIdx.x % L::LANES, npt = blockDim.x / L::LANES;
   const uint32_t n = redo[0];
   for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {  // block-uniform
     const uint32_t b = redo[1 + k];
     const uint32_t beg = begin[b], end = beg + count[b];
-    XYZZ<F> acc = XYZZ<F>::infinity();
-    for (uint32_t j = beg + threadIdx.x; j < end; j += blockDim.x) {
-      const uint32_t v = sorted[j];
-      Affine<F> p = load_vec(bases + (v & 0x7fffffffu));
-      if (v >> 31) p.y = p.y.neg();
-      acc.madd(p);
-    }
-    acc = block_tree_sum(acc, sh);
-    if (threadIdx.x == 0) {
+    typename L::P acc = L::P::infinity();
+    for (uint32_t j = beg + pt; j < end; j += npt) acc.madd(L::load_affine(bases, sorted[j], comp));
+    acc = lanes_tree_sum<L>(acc, sh, pt, npt, comp);
+    if (pt == 0) {
       // into: the accumulation was adding to an earlier MSM's bucket sums and left the listed buckets untouched
-      if (into) acc.add(load_vec(buckets + b));
-      store_vec(buckets + b, acc);
+      if (into) acc.add(L::load(buckets + b, comp));
+      L::store(buckets + b, acc, comp);
     }
     __syncthreads();
   }
@@ -640,6 +740,20 @@ k_accum_redo(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ b
     *ticket = 0;
   }
 }
+template <class F>
+__global__ void __launch_bounds__(64)
+k_accum_redo(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ begin,
+             const uint32_t* __restrict__ count, const uint32_t* __restrict__ sorted,
+             XYZZ<F>* __restrict__ buckets, uint32_t* __restrict__ redo, uint32_t* __restrict__ ticket, uint32_t into) {
+  accum_redo_body<OneLane<F>>(bases, begin, count, sorted, buckets, redo, ticket, into);
+}
+template <int UNUSED = 0>
+__global__ void __launch_bounds__(64, 2)
+k_accum_redo_g2_split(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __restrict__ begin,
+                      const uint32_t* __restrict__ count, const uint32_t* __restrict__ sorted,
+                      XYZZ<Fq2_28>* __restrict__ buckets, uint32_t* __restrict__ redo, uint32_t* __restrict__ ticket) {
+  accum_redo_body<LanePair>(bases, begin, count, sorted, buckets, redo, ticket, 0u);  // (no accumulate-into form for G2)
+}
 
 // Heavy buckets (repeated scalars, booleans: one bucket can hold 20 % of all points):
 // MSM_HSPLIT workgroups share one bucket, each reduces a sub-range with an LDS tree into
@@ -647,20 +761,6 @@ k_accum_redo(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ b
 // partial-slot capacity (pathological inputs) fall back to one workgroup per bucket.
 constexpr uint32_t MSM_HSPLIT = 64;
 constexpr uint32_t MSM_HEAVY_CAP = 1024;
-
-template <class F>
-__device__ __forceinline__ XYZZ<F> block_tree_sum(XYZZ<F> acc, XYZZ<F>* sh) {
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (uint32_t s = blockDim.x / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      acc.add(sh[threadIdx.x + s]);
-      sh[threadIdx.x] = acc;
-    }
-    __syncthreads();
-  }
-  return acc;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Round 5: the heavy buckets' additions in a kernel that RUNS BESIDE the light accumulation.
@@ -966,39 +1066,40 @@ __device__ __forceinline__ uint32_t heavy_nsplit(uint32_t h, uint32_t count, uin
   if (item0 + n > MSM_HPOOL) n = 1;  // pool exhausted (thousands of split buckets: pathological): unsplit
   return n;
 }
-template <class F>
-__global__ void __launch_bounds__(MSM_TREE_T)
-k_accum_heavy(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ begin,
-              const uint32_t* __restrict__ count, const uint32_t* __restrict__ heavy,
-              const uint32_t* __restrict__ sorted, XYZZ<F>* __restrict__ buckets,
-              XYZZ<F>* __restrict__ heavy_partial, uint32_t* __restrict__ ticket, uint32_t into, uint32_t h_first,
-              uint32_t h_limit, const uint32_t* __restrict__ hplan, const XYZZ<F>* __restrict__ pool_nc) {
+// The ticket of a split bucket: every lane of point 0 stores its part of the partial and fences, a barrier, then thread 0
+// takes the ticket -- a sequence that holds for any LANES ("thread 0 stores, fences and takes it" would for one lane only).
+template <class L>
+__device__ __forceinline__ void accum_heavy_body(const typename L::Base* __restrict__ bases, const uint32_t* __restrict__ begin,
+                                                 const uint32_t* __restrict__ count, const uint32_t* __restrict__ heavy,
+                                                 const uint32_t* __restrict__ sorted, typename L::Stored* __restrict__ buckets,
+                                                 typename L::Stored* __restrict__ heavy_partial, uint32_t* __restrict__ ticket,
+                                                 uint32_t into, uint32_t h_first, uint32_t h_limit, const uint32_t* __restrict__ hplan,
+                                                 const typename L::Stored* __restrict__ pool_nc) {
+  typedef typename L::P P;
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  XYZZ<F>* sh = reinterpret_cast<XYZZ<F>*>(lds_raw);
+  typename L::Stored* sh = reinterpret_cast<typename L::Stored*>(lds_raw);
   __shared__ uint32_t is_last;
-  // PARTIAL mode (hplan given and its mode word 0): the "points" of list entry h are the partial sums k_accum_heavy_nc left
-  // in pool_nc -- 64 per wave-item, in wave-item order -- and the list is the plan's; POINT mode: the kernel of rounds 1-4
+  const uint32_t pt = threadIdx.x / L::LANES, comp = threadIdx.x % L::LANES, npt = blockDim.x / L::LANES;
+  // PARTIAL mode (hplan given and its mode word 0): the "points" of list entry h are the partial sums k_accum_heavy_nc[_g2]
+  // left in pool_nc -- one per point of a wave, in wave-item order -- and the list is the plan's; POINT mode: the kernel of
+  // rounds 1-4
+  constexpr uint32_t PER_ITEM = 64 / L::LANES;
   const bool pmode = hplan != nullptr && hplan[3] == 0;
   const uint32_t* __restrict__ const ent = hplan + 4;
   const uint32_t pl_nc = pmode ? hplan[1] : 0u;
-  // a partial sum, or -- where its lane met P + P -- the lane's points again with the complete law
+  // a partial sum, or -- where its lane (pair) met P + P -- that lane's points again with the complete law
   auto partial_at = [&](uint32_t h, uint32_t j) {
-    XYZZ<F> v = load_vec(pool_nc + j);
-    uint32_t o = 0;
-#pragma unroll
-    for (int i = 0; i < F::NL; i++) o |= (uint32_t)v.zz.l[i];
-    if (o == 0 && v.zzz.l[0] == 1) {
-      const uint32_t it = j >> 6, ln = j & 63u;
+    P v = L::load(pool_nc + j, comp);
+    bool empty;
+    if (L::is_marker(v, comp, &empty)) {
+      const uint32_t it = j / PER_ITEM, ln = j % PER_ITEM;
       const uint32_t beg = ent[4 * h + 1], cnt = ent[4 * h + 2], first = ent[4 * h + 3];
-      const uint32_t w0 = beg + (it - first) * 64u * pl_nc;
-      const uint32_t w1 = (w0 + 64u * pl_nc < beg + cnt) ? w0 + 64u * pl_nc : beg + cnt;
-      v = XYZZ<F>::infinity();
-      for (uint32_t jj = w0 + ln; jj < w1; jj += 64) {
-        const uint32_t sv = sorted[jj];
-        Affine<F> p = load_vec(bases + (sv & 0x7fffffffu));
-        if (sv >> 31) p.y = p.y.neg();
-        v.madd(p);
-      }
+      const uint32_t w0 = beg + (it - first) * PER_ITEM * pl_nc;
+      const uint32_t w1 = (w0 + PER_ITEM * pl_nc < beg + cnt) ? w0 + PER_ITEM * pl_nc : beg + cnt;
+      v = P::infinity();
+      for (uint32_t jj = w0 + ln; jj < w1; jj += PER_ITEM) v.madd(L::load_affine(bases, sorted[jj], comp));
+    } else if (empty) {
+      v = P::infinity();  // (what add() takes it for anyway; without it k_accum_heavy<Fq28> allocates 315 registers, not 308)
     }
     return v;
   };
@@ -1007,11 +1108,6 @@ k_accum_heavy(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ 
   // first MSM_HEAVY_CAP entries go to a (MSM_HSPLIT, 8) grid and the rest to a second launch with one workgroup per
   // list entry (a (MSM_HSPLIT, 8) grid would walk them with 8 workgroups)
   const uint32_t n_heavy = pmode ? hplan[2] : (heavy[0] < h_limit ? heavy[0] : h_limit);
-  // into: the bucket's sum is added to what an earlier MSM left in the bucket (complete addition, one thread)
-  auto put = [&](uint32_t b, XYZZ<F> v) {
-    if (into) v.add(load_vec(buckets + b));
-    store_vec(buckets + b, v);
-  };
   // Work items = (bucket, sub-range) pairs, numbered through the list and dealt round-robin to ALL workgroups of the grid.
   // (Rounds 1-3 gave grid row y the buckets y, y + 8, ... and column x the sub-range x: the 64 buckets of a group of small
   // proofs -- one per proof, ~600 points = 2 sub-ranges each -- were walked 8 at a time by 2 of the 64 columns: 5.8 ms per
@@ -1022,14 +1118,15 @@ k_accum_heavy(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ 
   const bool tail = h_first >= MSM_HEAVY_CAP;
   for (uint32_t h = tail ? h_first + wg : h_first; h < n_heavy; h += tail ? n_wg : 1u) {
     const uint32_t b = pmode ? ent[4 * h] : heavy[1 + h];
-    // (partial mode: positions in pool_nc -- 64 partial sums per wave-item of the entry)
-    const uint32_t cnt = pmode ? (ent[4 * (h + 1) + 3] - ent[4 * h + 3]) * 64u : count[b];
-    const uint32_t beg0 = pmode ? ent[4 * h + 3] * 64u : begin[b];
-    // as many sub-ranges as the bucket can feed: ~4 points per thread before the tree (a bucket of 400 points on
-    // all 64 x 128 threads is 64 trees of points at infinity: measured 10 % of all instructions of a 2^14 group).
+    // (partial mode: positions in pool_nc -- PER_ITEM partial sums per wave-item of the entry)
+    const uint32_t cnt = pmode ? (ent[4 * (h + 1) + 3] - ent[4 * h + 3]) * PER_ITEM : count[b];
+    const uint32_t beg0 = pmode ? ent[4 * h + 3] * PER_ITEM : begin[b];
+    // as many sub-ranges as the bucket can feed: ~4 points per thread (lane pair) of the MSM_TREE_T before the tree (a
+    // bucket of 400 points on all 64 x 128 threads is 64 trees of points at infinity: measured 10 % of all instructions of
+    // a 2^14 group).
     // (8 points per thread -- one workgroup, no partials and no second tree for the 600 bit variables of a small
     // proof -- measured no better: 2^14 2 501 against 2 554-2 573 proofs/s.)
-    const uint32_t nsplit = tail ? 1u : heavy_nsplit(h, cnt, 4 * MSM_TREE_T, item0);
+    const uint32_t nsplit = tail ? 1u : heavy_nsplit(h, cnt, 4 * MSM_TREE_T / L::LANES, item0);
     const uint32_t base = item0;
     // this workgroup's sub-ranges of the bucket: item numbers base + r = wg (mod n_wg)
     const uint32_t r0 = tail ? 0u : (wg + n_wg - base % n_wg) % n_wg;
@@ -1042,175 +1139,149 @@ k_accum_heavy(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ 
         end = (sb + len < end) ? sb + len : end;
         beg = sb < end ? sb : end;
       }
-      XYZZ<F> acc = XYZZ<F>::infinity();
+      P acc = P::infinity();
       if (pmode) {
-        for (uint32_t j = beg + threadIdx.x; j < end; j += blockDim.x) acc.add(partial_at(h, j));
+        for (uint32_t j = beg + pt; j < end; j += npt) acc.add(partial_at(h, j));
       } else {
-        for (uint32_t j = beg + threadIdx.x; j < end; j += blockDim.x) {
-          const uint32_t v = sorted[j];
-          Affine<F> p = load_vec(bases + (v & 0x7fffffffu));
-          if (v >> 31) p.y = p.y.neg();
-          acc.madd(p);
-        }
+        for (uint32_t j = beg + pt; j < end; j += npt) acc.madd(L::load_affine(bases, sorted[j], comp));
       }
-      acc = block_tree_sum(acc, sh);
+      acc = lanes_tree_sum<L>(acc, sh, pt, npt, comp);
       if (nsplit == 1) {
-        if (threadIdx.x == 0) put(b, acc);
-      } else {
-        if (threadIdx.x == 0) {
-          store_vec(heavy_partial + (size_t)base + r, acc);
-          __threadfence();  // the partial is visible device-wide before the ticket is taken
-          is_last = atomicAdd(ticket + h, 1u) == nsplit - 1 ? 1u : 0u;
+        if (pt == 0) {
+          // into: the bucket's sum is added to what an earlier MSM left in the bucket (complete addition, the lanes of point 0)
+          // (spelt out here and below: behind a lambda the same two lines cost 944 B of scratch per lane in the lane-pair kernel)
+          if (into) acc.add(L::load(buckets + b, comp));
+          L::store(buckets + b, acc, comp);
         }
+      } else {
+        if (pt == 0) {
+          L::store(heavy_partial + (size_t)base + r, acc, comp);
+          __threadfence();  // each lane's part of the partial is visible device-wide ...
+        }
+        __syncthreads();  // ... before the ticket is taken
+        if (threadIdx.x == 0) is_last = atomicAdd(ticket + h, 1u) == nsplit - 1 ? 1u : 0u;
         __syncthreads();
         if (is_last) {  // block-uniform
           __threadfence();
-          XYZZ<F> v = XYZZ<F>::infinity();
-          for (uint32_t k = threadIdx.x; k < nsplit; k += blockDim.x) v.add(load_vec(heavy_partial + (size_t)base + k));
-          v = block_tree_sum(v, sh);
-          if (threadIdx.x == 0) {
-            put(b, v);
-            ticket[h] = 0;
+          P v = P::infinity();
+          for (uint32_t k = pt; k < nsplit; k += npt) v.add(L::load(heavy_partial + (size_t)base + k, comp));
+          v = lanes_tree_sum<L>(v, sh, pt, npt, comp);
+          if (pt == 0) {
+            if (into) v.add(L::load(buckets + b, comp));
+            L::store(buckets + b, v, comp);
           }
+          if (threadIdx.x == 0) ticket[h] = 0;
         }
       }
       __syncthreads();
     }
   }
 }
+template <class F>
+__global__ void __launch_bounds__(MSM_TREE_T)
+k_accum_heavy(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ begin,
+              const uint32_t* __restrict__ count, const uint32_t* __restrict__ heavy,
+              const uint32_t* __restrict__ sorted, XYZZ<F>* __restrict__ buckets,
+              XYZZ<F>* __restrict__ heavy_partial, uint32_t* __restrict__ ticket, uint32_t into, uint32_t h_first,
+              uint32_t h_limit, const uint32_t* __restrict__ hplan, const XYZZ<F>* __restrict__ pool_nc) {
+  accum_heavy_body<OneLane<F>>(bases, begin, count, heavy, sorted, buckets, heavy_partial, ticket, into, h_first, h_limit, hplan, pool_nc);
+}
+template <int UNUSED = 0>
+__global__ void __launch_bounds__(MSM_TREE_T, 2)
+k_accum_heavy_g2_split(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __restrict__ begin,
+                       const uint32_t* __restrict__ count, const uint32_t* __restrict__ heavy,
+                       const uint32_t* __restrict__ sorted, XYZZ<Fq2_28>* __restrict__ buckets,
+                       XYZZ<Fq2_28>* __restrict__ heavy_partial, uint32_t* __restrict__ ticket, uint32_t h_first,
+                       uint32_t h_limit, const uint32_t* __restrict__ hplan, const XYZZ<Fq2_28>* __restrict__ pool_nc) {
+  accum_heavy_body<LanePair>(bases, begin, count, heavy, sorted, buckets, heavy_partial, ticket, 0u, h_first, h_limit, hplan, pool_nc);
+}
 
-// thread t handles buckets [t*SEG, (t+1)*SEG) of one window (global segment id)
+// point t handles buckets [t*SEG, (t+1)*SEG) of one window (global segment id)
 // buckets2 (optional): the bucket array of a SECOND MSM over the same bucket set whose result is only ever added to this
 // one's (the prover's L and H queries: C = ... + L + H).  Its buckets join the running sum here -- three additions per bucket
 // for the pair instead of two each, and one tree sum / host combine instead of two -- and nothing else of the two MSMs
 // knows about the other: both accumulate into their own arrays with the ordinary kernels.
-template <class F>
-__global__ void __launch_bounds__(256)
-k_segreduce(const XYZZ<F>* __restrict__ buckets, XYZZ<F>* __restrict__ segsum, XYZZ<F>* __restrict__ segw,
-            uint32_t total_segs, int seg, const XYZZ<F>* __restrict__ buckets2, const XYZZ<F>* __restrict__ buckets3) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+template <class L>
+__device__ __forceinline__ void segreduce_body(const typename L::Stored* __restrict__ buckets, typename L::Stored* __restrict__ segsum,
+                                               typename L::Stored* __restrict__ segw, uint32_t total_segs, int seg,
+                                               const typename L::Stored* __restrict__ buckets2,
+                                               const typename L::Stored* __restrict__ buckets3) {
+  const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t t = gt / L::LANES, comp = gt % L::LANES;
   if (t >= total_segs) return;
-  XYZZ<F> run = XYZZ<F>::infinity();
-  XYZZ<F> acc = XYZZ<F>::infinity();
+  typename L::P run = L::P::infinity();
+  typename L::P acc = L::P::infinity();
   for (int i = seg - 1; i >= 0; i--) {
-    XYZZ<F> bk = load_vec(buckets + (size_t)t * seg + i);
+    typename L::P bk = L::load(buckets + (size_t)t * seg + i, comp);
     run.add(bk);
     if (buckets2) {
-      bk = load_vec(buckets2 + (size_t)t * seg + i);
+      bk = L::load(buckets2 + (size_t)t * seg + i, comp);
       run.add(bk);
     }
     if (buckets3) {
-      bk = load_vec(buckets3 + (size_t)t * seg + i);
+      bk = L::load(buckets3 + (size_t)t * seg + i, comp);
       run.add(bk);
     }
     acc.add(run);
   }
-  store_vec(segsum + t, run);
-  store_vec(segw + t, acc);
+  L::store(segsum + t, run, comp);
+  L::store(segw + t, acc, comp);
 }
-
-// The same kernel at two waves per SIMD (256 registers, 656 B of scratch instead of 464): for the reductions that have the chip to
+template <class F>
+__global__ void __launch_bounds__(256)
+k_segreduce(const XYZZ<F>* __restrict__ buckets, XYZZ<F>* __restrict__ segsum, XYZZ<F>* __restrict__ segw,
+            uint32_t total_segs, int seg, const XYZZ<F>* __restrict__ buckets2, const XYZZ<F>* __restrict__ buckets3) {
+  segreduce_body<OneLane<F>>(buckets, segsum, segw, total_segs, seg, buckets2, buckets3);
+}
+// The same at two waves per SIMD (256 registers, 656 B of scratch instead of 464): for the reductions that have the chip to
 // themselves and enough waves to use the room -- the 13 x 2^19 buckets of the big windowed plans, 5.66 -> 4.98 ms at 2^26 terms.
 // (The prover's and the small plans' reductions keep the form above: they run beside accumulations or are latency chains.)
 template <class F>
 __global__ void __launch_bounds__(256, 2)
 k_segreduce_w2(const XYZZ<F>* __restrict__ buckets, XYZZ<F>* __restrict__ segsum, XYZZ<F>* __restrict__ segw,
             uint32_t total_segs, int seg, const XYZZ<F>* __restrict__ buckets2, const XYZZ<F>* __restrict__ buckets3) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total_segs) return;
-  XYZZ<F> run = XYZZ<F>::infinity();
-  XYZZ<F> acc = XYZZ<F>::infinity();
-  for (int i = seg - 1; i >= 0; i--) {
-    XYZZ<F> bk = load_vec(buckets + (size_t)t * seg + i);
-    run.add(bk);
-    if (buckets2) {
-      bk = load_vec(buckets2 + (size_t)t * seg + i);
-      run.add(bk);
-    }
-    if (buckets3) {
-      bk = load_vec(buckets3 + (size_t)t * seg + i);
-      run.add(bk);
-    }
-    acc.add(run);
-  }
-  store_vec(segsum + t, run);
-  store_vec(segw + t, acc);
+  segreduce_body<OneLane<F>>(buckets, segsum, segw, total_segs, seg, buckets2, buckets3);
 }
-
-// lane-pair split forms of the two reduction kernels for G2 (see k_accum_g2_split)
-__device__ __forceinline__ XYZZ<Fq2P> ld_xyzz_split(const XYZZ<Fq2_28>* p, uint32_t comp) {
-  const Fq28* s = reinterpret_cast<const Fq28*>(p);
-  XYZZ<Fq2P> r;
-  r.x.v = ld_comp(s + comp);
-  r.y.v = ld_comp(s + 2 + comp);
-  r.zz.v = ld_comp(s + 4 + comp);
-  r.zzz.v = ld_comp(s + 6 + comp);
-  return r;
-}
-__device__ __forceinline__ void st_xyzz_split(XYZZ<Fq2_28>* p, const XYZZ<Fq2P>& v, uint32_t comp) {
-  Fq28* d = reinterpret_cast<Fq28*>(p);
-  st_comp(d + comp, v.x.v);
-  st_comp(d + 2 + comp, v.y.v);
-  st_comp(d + 4 + comp, v.zz.v);
-  st_comp(d + 6 + comp, v.zzz.v);
-}
-
 template <int UNUSED = 0>
 __global__ void __launch_bounds__(256, 2)
 k_segreduce_g2_split(const XYZZ<Fq2_28>* __restrict__ buckets, XYZZ<Fq2_28>* __restrict__ segsum,
                      XYZZ<Fq2_28>* __restrict__ segw, uint32_t total_segs, int seg) {
-  const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t t = gt >> 1, comp = gt & 1u;
-  if (t >= total_segs) return;  // pair-uniform
-  XYZZ<Fq2P> run = XYZZ<Fq2P>::infinity();
-  XYZZ<Fq2P> acc = XYZZ<Fq2P>::infinity();
-  for (int i = seg - 1; i >= 0; i--) {
-    XYZZ<Fq2P> bk = ld_xyzz_split(buckets + (size_t)t * seg + i, comp);
-    run.add(bk);
-    acc.add(run);
-  }
-  st_xyzz_split(segsum + t, run, comp);
-  st_xyzz_split(segw + t, acc, comp);
+  segreduce_body<LanePair>(buckets, segsum, segw, total_segs, seg, nullptr, nullptr);
 }
 
 // Second running-sum level.  The tree sums below weight segment t of a window by t through bit decomposition: every
 // segsum entry is added ~ log2(segments) / 2 times.  With t = 16 u + k,
 //   sum_t t segsum_t = 16 sum_u u segsum2_u + sum_u segt2_u,   segsum2_u = sum_k segsum_(16u+k),  segt2_u = sum_k k segsum_(16u+k),
-// so a thread per super-segment u forms both by the running sums of k_segreduce (31 additions per 16 segments) and the bit
+// so a point per super-segment u forms both by the running sums of k_segreduce (31 additions per 16 segments) and the bit
 // jobs walk the 16 x shorter list segsum2; segt2 is one more plain job.  (The plain sum of segw stays what it was: every
 // entry is added once either way.)  The segment lists of the windows lie back to back and are multiples of 16 long, so
 // super-segment u of the array is super-segment u mod (segments / 16) of its window.
-template <class F>
-__global__ void __launch_bounds__(256)
-k_segreduce2(const XYZZ<F>* __restrict__ segsum, XYZZ<F>* __restrict__ segsum2, XYZZ<F>* __restrict__ segt2, uint32_t total_segs2) {
-  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+template <class L>
+__device__ __forceinline__ void segreduce2_body(const typename L::Stored* __restrict__ segsum, typename L::Stored* __restrict__ segsum2,
+                                                typename L::Stored* __restrict__ segt2, uint32_t total_segs2) {
+  const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t u = gt / L::LANES, comp = gt % L::LANES;
   if (u >= total_segs2) return;
-  XYZZ<F> run = XYZZ<F>::infinity();
-  XYZZ<F> acc = XYZZ<F>::infinity();
+  typename L::P run = L::P::infinity();
+  typename L::P acc = L::P::infinity();
   for (int k = (1 << MSM_SEG2_LOG) - 1; k >= 0; k--) {
-    XYZZ<F> v = load_vec(segsum + ((size_t)u << MSM_SEG2_LOG) + k);
+    typename L::P v = L::load(segsum + ((size_t)u << MSM_SEG2_LOG) + k, comp);
     run.add(v);
     if (k) acc.add(run);  // weight k, not k + 1: segment 0 of a super-segment counts in the plain sum only
   }
-  store_vec(segsum2 + u, run);
-  store_vec(segt2 + u, acc);
+  L::store(segsum2 + u, run, comp);
+  L::store(segt2 + u, acc, comp);
+}
+template <class F>
+__global__ void __launch_bounds__(256)
+k_segreduce2(const XYZZ<F>* __restrict__ segsum, XYZZ<F>* __restrict__ segsum2, XYZZ<F>* __restrict__ segt2, uint32_t total_segs2) {
+  segreduce2_body<OneLane<F>>(segsum, segsum2, segt2, total_segs2);
 }
 template <int UNUSED = 0>
 __global__ void __launch_bounds__(256, 2)
 k_segreduce2_g2_split(const XYZZ<Fq2_28>* __restrict__ segsum, XYZZ<Fq2_28>* __restrict__ segsum2, XYZZ<Fq2_28>* __restrict__ segt2,
                       uint32_t total_segs2) {
-  const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t u = gt >> 1, comp = gt & 1u;
-  if (u >= total_segs2) return;  // pair-uniform
-  XYZZ<Fq2P> run = XYZZ<Fq2P>::infinity();
-  XYZZ<Fq2P> acc = XYZZ<Fq2P>::infinity();
-  for (int k = (1 << MSM_SEG2_LOG) - 1; k >= 0; k--) {
-    XYZZ<Fq2P> v = ld_xyzz_split(segsum + ((size_t)u << MSM_SEG2_LOG) + k, comp);
-    run.add(v);
-    if (k) acc.add(run);
-  }
-  st_xyzz_split(segsum2 + u, run, comp);
-  st_xyzz_split(segt2 + u, acc, comp);
+  segreduce2_body<LanePair>(segsum, segsum2, segt2, total_segs2);
 }
 
 // What the tree-sum kernels read when a second level ran (t_job < 0: none): the bit jobs and the plain job walk segsum2
@@ -1245,281 +1316,89 @@ __device__ __forceinline__ const P* tree_job_list(int job, int w, const P* segsu
 // nchunk > 1 (small plans, where the reduction is a latency chain and the chip is empty): workgroup z sums the z-th
 // slice of the list into stage[(w * njobs + job) * nchunk + z]; k_treesum_final adds the slices.  A list of 2^13 segments
 // then costs 2 + 7 + 5 dependent additions instead of 64 + 7.
+// One loop over the list for whole jobs and bit jobs, with a select on `whole`: k_treesum<Fq28> is 24 471 instructions
+// with it, 33 592 with a loop per kind of job.
+template <class L>
+__device__ __forceinline__ void treesum_body(const typename L::Stored* __restrict__ segsum, const typename L::Stored* __restrict__ segw,
+                                             uint32_t segs_per_win, typename L::Host* __restrict__ partial, int plain_job,
+                                             typename L::Stored* __restrict__ stage, typename L::Host* __restrict__ partial_host,
+                                             const TreeLevel2<typename L::Stored>& l2) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  typename L::Stored* sh = reinterpret_cast<typename L::Stored*>(lds_raw);
+  const int job = blockIdx.x;
+  const int w = blockIdx.y;
+  const uint32_t nchunk = gridDim.z, z = blockIdx.z;
+  const uint32_t pt = threadIdx.x / L::LANES, comp = threadIdx.x % L::LANES, npt = blockDim.x / L::LANES;
+  uint32_t len;
+  bool whole;
+  const typename L::Stored* src = tree_job_list(job, w, segsum, segw, segs_per_win, plain_job, l2, &len, &whole);
+  const uint32_t per = (len + nchunk - 1) / nchunk;
+  // (a list shorter than the slices of job 0 leaves the last slices empty: lo >= hi)
+  const uint32_t lo = z * per, hi = lo + per < len ? lo + per : len;
+  // bit job: enumerate only the segments whose bit (job - 1) is set, so that no lane idles through an addition
+  const uint32_t b = whole ? 0u : (uint32_t)(job - 1), lowmask = (1u << b) - 1u;
+  typename L::P acc = L::P::infinity();
+  for (uint32_t u = lo + pt; u < hi; u += npt) {
+    const uint32_t t = whole ? u : (((u & ~lowmask) << 1) | (1u << b) | (u & lowmask));
+    typename L::P v = L::load(src + t, comp);
+    acc.add(v);
+  }
+  acc = lanes_tree_sum<L>(acc, sh, pt, npt, comp);
+  if (pt == 0) {
+    if (nchunk == 1) {
+      // device copy (the RCCL exchange gathers it) and, directly, the pinned host slot the combining thread reads: no
+      // device-to-host copy behind the reduction (it ran as a blit kernel, 0.3 ms of waiting for SIMDs per MSM)
+      L::store_host(partial + (size_t)w * gridDim.x + job, acc, comp);
+      L::store_host(partial_host + (size_t)w * gridDim.x + job, acc, comp);
+    } else {
+      L::store(stage + ((size_t)w * gridDim.x + job) * nchunk + z, acc, comp);
+    }
+  }
+}
+// grid = (njobs, nwin), nchunk <= points per workgroup (a power of two) <= MSM_TREE_T: adds the slices of one (window, job)
+template <class L>
+__device__ __forceinline__ void treesum_final_body(const typename L::Stored* __restrict__ stage, uint32_t nchunk,
+                                                   typename L::Host* __restrict__ partial, typename L::Host* __restrict__ partial_host) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  typename L::Stored* sh = reinterpret_cast<typename L::Stored*>(lds_raw);
+  const size_t idx = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  const uint32_t pt = threadIdx.x / L::LANES, comp = threadIdx.x % L::LANES, npt = blockDim.x / L::LANES;
+  typename L::P acc = L::P::infinity();
+  if (pt < nchunk) acc = L::load(stage + idx * nchunk + pt, comp);
+  acc = lanes_tree_sum<L>(acc, sh, pt, npt, comp);
+  if (pt == 0) {
+    L::store_host(partial + idx, acc, comp);
+    L::store_host(partial_host + idx, acc, comp);
+  }
+}
 template <class F>
 __global__ void __launch_bounds__(MSM_TREE_T)
 k_treesum(const XYZZ<F>* __restrict__ segsum, const XYZZ<F>* __restrict__ segw, uint32_t segs_per_win,
           XYZZ<typename HostFieldOf<F>::type>* __restrict__ partial, int plain_job, XYZZ<F>* __restrict__ stage,
           XYZZ<typename HostFieldOf<F>::type>* __restrict__ partial_host, TreeLevel2<XYZZ<F>> l2) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  XYZZ<F>* sh = reinterpret_cast<XYZZ<F>*>(lds_raw);
-  const int job = blockIdx.x;
-  const int w = blockIdx.y;
-  const uint32_t nchunk = gridDim.z, z = blockIdx.z;
-  uint32_t len;
-  bool whole;
-  const XYZZ<F>* src = tree_job_list(job, w, segsum, segw, segs_per_win, plain_job, l2, &len, &whole);
-  const uint32_t per = (len + nchunk - 1) / nchunk;
-  // (a list shorter than the slices of job 0 leaves the last slices empty: lo >= hi)
-  const uint32_t lo = z * per, hi = lo + per < len ? lo + per : len;
-  XYZZ<F> acc = XYZZ<F>::infinity();
-  if (whole) {
-    for (uint32_t t = lo + threadIdx.x; t < hi; t += blockDim.x) {
-      XYZZ<F> v = load_vec(src + t);
-      acc.add(v);
-    }
-  } else {
-    // bit job: enumerate only the segments whose bit (job - 1) is set, so that no lane idles through an addition
-    const uint32_t b = (uint32_t)(job - 1), lowmask = (1u << b) - 1u;
-    for (uint32_t u = lo + threadIdx.x; u < hi; u += blockDim.x) {
-      const uint32_t t = ((u & ~lowmask) << 1) | (1u << b) | (u & lowmask);
-      XYZZ<F> v = load_vec(src + t);
-      acc.add(v);
-    }
-  }
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (uint32_t s = blockDim.x / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      acc.add(sh[threadIdx.x + s]);
-      sh[threadIdx.x] = acc;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    if (nchunk == 1) {
-      XYZZ<typename HostFieldOf<F>::type> o = {fq_from_fq28(acc.x), fq_from_fq28(acc.y), fq_from_fq28(acc.zz),
-                                               fq_from_fq28(acc.zzz)};
-      // device copy (the RCCL exchange gathers it) and, directly, the pinned host slot the combining thread reads: no
-      // device-to-host copy behind the reduction (it ran as a blit kernel, 0.3 ms of waiting for SIMDs per MSM)
-      store_vec(partial + (size_t)w * gridDim.x + job, o);
-      store_vec(partial_host + (size_t)w * gridDim.x + job, o);
-    } else {
-      store_vec(stage + ((size_t)w * gridDim.x + job) * nchunk + z, acc);
-    }
-  }
+  treesum_body<OneLane<F>>(segsum, segw, segs_per_win, partial, plain_job, stage, partial_host, l2);
 }
-
-// grid = (njobs, nwin), nchunk <= blockDim.x (a power of two) <= MSM_TREE_T: adds the slices of one (window, job)
 template <class F>
 __global__ void __launch_bounds__(MSM_TREE_T)
 k_treesum_final(const XYZZ<F>* __restrict__ stage, uint32_t nchunk, XYZZ<typename HostFieldOf<F>::type>* __restrict__ partial,
                 XYZZ<typename HostFieldOf<F>::type>* __restrict__ partial_host) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  XYZZ<F>* sh = reinterpret_cast<XYZZ<F>*>(lds_raw);
-  const size_t idx = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-  XYZZ<F> acc = XYZZ<F>::infinity();
-  if (threadIdx.x < nchunk) acc = load_vec(stage + idx * nchunk + threadIdx.x);
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (uint32_t s = blockDim.x / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      acc.add(sh[threadIdx.x + s]);
-      sh[threadIdx.x] = acc;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    XYZZ<typename HostFieldOf<F>::type> o = {fq_from_fq28(acc.x), fq_from_fq28(acc.y), fq_from_fq28(acc.zz),
-                                             fq_from_fq28(acc.zzz)};
-    store_vec(partial + idx, o);
-    store_vec(partial_host + idx, o);
-  }
+  treesum_final_body<OneLane<F>>(stage, nchunk, partial, partial_host);
 }
-
-// Lane-pair forms of the two tree-sum kernels for G2 (see k_accum_g2_split): a pair owns one list element, so the
-// unsplit form's 330-register additions (one wave per SIMD, 45-60 us each in a latency chain) become G1-sized ones.
-// Used for the sliced (small-plan) case, where the tree sums ARE the latency of a proof; blockDim.x / 2 pairs per workgroup.
-__device__ __forceinline__ void st_host_split(XYZZ<Fq2>* dst, const XYZZ<Fq2P>& v, uint32_t comp) {
-  Fq* d = reinterpret_cast<Fq*>(dst);  // x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1
-  d[comp] = fq_from_fq28(v.x.v);
-  d[2 + comp] = fq_from_fq28(v.y.v);
-  d[4 + comp] = fq_from_fq28(v.zz.v);
-  d[6 + comp] = fq_from_fq28(v.zzz.v);
-}
-__device__ __forceinline__ XYZZ<Fq2P> pair_tree_sum(XYZZ<Fq2P> acc, XYZZ<Fq2_28>* sh, uint32_t pair, uint32_t npair, uint32_t comp) {
-  st_xyzz_split(sh + pair, acc, comp);
-  __syncthreads();
-  for (uint32_t s = npair / 2; s > 0; s >>= 1) {
-    if (pair < s) {  // pair-uniform
-      XYZZ<Fq2P> o = ld_xyzz_split(sh + pair + s, comp);
-      acc.add(o);
-      st_xyzz_split(sh + pair, acc, comp);
-    }
-    __syncthreads();
-  }
-  return acc;
-}
+// The lane-pair tree sums for G2: a pair owns one list element, so the unsplit form's 330-register additions (one wave per
+// SIMD, 45-60 us each in a latency chain) become G1-sized ones.  For the sliced (small-plan) case, where the tree sums ARE
+// the latency of a proof, and for the big plans; blockDim.x / 2 pairs per workgroup.
 template <int UNUSED = 0>
 __global__ void __launch_bounds__(2 * MSM_TREE_T, 2)
 k_treesum_g2_split(const XYZZ<Fq2_28>* __restrict__ segsum, const XYZZ<Fq2_28>* __restrict__ segw, uint32_t segs_per_win,
                    XYZZ<Fq2>* __restrict__ partial, int plain_job, XYZZ<Fq2_28>* __restrict__ stage, XYZZ<Fq2>* __restrict__ partial_host,
                    TreeLevel2<XYZZ<Fq2_28>> l2) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  XYZZ<Fq2_28>* sh = reinterpret_cast<XYZZ<Fq2_28>*>(lds_raw);
-  const int job = blockIdx.x;
-  const int w = blockIdx.y;
-  const uint32_t nchunk = gridDim.z, z = blockIdx.z;
-  const uint32_t pair = threadIdx.x >> 1, comp = threadIdx.x & 1u, npair = blockDim.x >> 1;
-  uint32_t len;
-  bool whole;
-  const XYZZ<Fq2_28>* src = tree_job_list(job, w, segsum, segw, segs_per_win, plain_job, l2, &len, &whole);
-  const uint32_t per = (len + nchunk - 1) / nchunk;
-  const uint32_t lo = z * per, hi = lo + per < len ? lo + per : len;
-  const uint32_t b = whole ? 0u : (uint32_t)(job - 1), lowmask = (1u << b) - 1u;
-  XYZZ<Fq2P> acc = XYZZ<Fq2P>::infinity();
-  for (uint32_t u = lo + pair; u < hi; u += npair) {
-    const uint32_t t = whole ? u : (((u & ~lowmask) << 1) | (1u << b) | (u & lowmask));
-    XYZZ<Fq2P> v = ld_xyzz_split(src + t, comp);
-    acc.add(v);
-  }
-  acc = pair_tree_sum(acc, sh, pair, npair, comp);
-  if (pair == 0) {
-    if (nchunk == 1)
-    {
-      st_host_split(partial + (size_t)w * gridDim.x + job, acc, comp);
-      st_host_split(partial_host + (size_t)w * gridDim.x + job, acc, comp);
-    }
-    else
-      st_xyzz_split(stage + ((size_t)w * gridDim.x + job) * nchunk + z, acc, comp);
-  }
+  treesum_body<LanePair>(segsum, segw, segs_per_win, partial, plain_job, stage, partial_host, l2);
 }
 template <int UNUSED = 0>
 __global__ void __launch_bounds__(2 * MSM_TREE_T, 2)
 k_treesum_final_g2_split(const XYZZ<Fq2_28>* __restrict__ stage, uint32_t nchunk, XYZZ<Fq2>* __restrict__ partial,
                          XYZZ<Fq2>* __restrict__ partial_host) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  XYZZ<Fq2_28>* sh = reinterpret_cast<XYZZ<Fq2_28>*>(lds_raw);
-  const size_t idx = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-  const uint32_t pair = threadIdx.x >> 1, comp = threadIdx.x & 1u, npair = blockDim.x >> 1;
-  XYZZ<Fq2P> acc = XYZZ<Fq2P>::infinity();
-  if (pair < nchunk) acc = ld_xyzz_split(stage + idx * nchunk + pair, comp);
-  acc = pair_tree_sum(acc, sh, pair, npair, comp);
-  if (pair == 0) {
-    st_host_split(partial + idx, acc, comp);
-    st_host_split(partial_host + idx, acc, comp);
-  }
-}
-
-// Lane-pair forms of the heavy-bucket and redo kernels for G2: same logic as k_accum_heavy / k_accum_redo with a lane
-// pair per point (the unsplit forms are 330-register kernels with 55-75 us per dependent addition: 0.8 ms for one
-// 600-point bucket of a 2^14 proof, on the critical path of the G2 reduction; and 0.1 ms to place an EMPTY redo kernel).
-__device__ __forceinline__ Affine<Fq2P> ld_affine_split(const Affine<Fq2_28>* bases, uint32_t v, uint32_t comp) {
-  const Fq28* src = reinterpret_cast<const Fq28*>(bases + (v & 0x7fffffffu));  // x.c0 x.c1 y.c0 y.c1
-  Affine<Fq2P> p;
-  p.x.v = ld_comp(src + comp);
-  p.y.v = ld_comp(src + 2 + comp);
-  if (v >> 31) p.y = p.y.neg();
-  return p;
-}
-template <int UNUSED = 0>
-__global__ void __launch_bounds__(MSM_TREE_T, 2)
-k_accum_heavy_g2_split(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __restrict__ begin,
-                       const uint32_t* __restrict__ count, const uint32_t* __restrict__ heavy,
-                       const uint32_t* __restrict__ sorted, XYZZ<Fq2_28>* __restrict__ buckets,
-                       XYZZ<Fq2_28>* __restrict__ heavy_partial, uint32_t* __restrict__ ticket, uint32_t h_first,
-                       uint32_t h_limit, const uint32_t* __restrict__ hplan, const XYZZ<Fq2_28>* __restrict__ pool_nc) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  XYZZ<Fq2_28>* sh = reinterpret_cast<XYZZ<Fq2_28>*>(lds_raw);
-  __shared__ uint32_t is_last;
-  const uint32_t pair = threadIdx.x >> 1, comp = threadIdx.x & 1u, npair = blockDim.x >> 1;
-  // PARTIAL / POINT mode: see k_accum_heavy (here 32 partial sums per wave-item, one per lane pair of k_accum_heavy_nc_g2)
-  const bool pmode = hplan != nullptr && hplan[3] == 0;
-  const uint32_t* __restrict__ const ent = hplan + 4;
-  const uint32_t pl_nc = pmode ? hplan[1] : 0u;
-  auto partial_at = [&](uint32_t h, uint32_t j) {  // pair-uniform
-    XYZZ<Fq2P> v = ld_xyzz_split(pool_nc + j, comp);
-    uint32_t o = 0;
-#pragma unroll
-    for (int i = 0; i < Fq28::NL; i++) o |= (uint32_t)v.zz.v.l[i];
-    uint32_t mk = (comp == 0 && v.zzz.v.l[0] == 1) ? 1u : 0u;
-    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
-    mk |= (uint32_t)__builtin_amdgcn_mov_dpp((int)mk, 0xB1, 0xF, 0xF, true);
-    if (o == 0 && mk == 1) {
-      const uint32_t it = j >> 5, pr = j & 31u;
-      const uint32_t beg = ent[4 * h + 1], cnt = ent[4 * h + 2], first = ent[4 * h + 3];
-      const uint32_t w0 = beg + (it - first) * 32u * pl_nc;
-      const uint32_t w1 = (w0 + 32u * pl_nc < beg + cnt) ? w0 + 32u * pl_nc : beg + cnt;
-      v = XYZZ<Fq2P>::infinity();
-      for (uint32_t jj = w0 + pr; jj < w1; jj += 32) v.madd(ld_affine_split(bases, sorted[jj], comp));
-    } else if (o == 0) {
-      v = XYZZ<Fq2P>::infinity();
-    }
-    return v;
-  };
-  const uint32_t n_heavy = pmode ? hplan[2] : (heavy[0] < h_limit ? heavy[0] : h_limit);  // list range [h_first, h_limit): see k_accum_heavy
-  const uint32_t n_wg = gridDim.x * gridDim.y, wg = blockIdx.y * gridDim.x + blockIdx.x;  // flat deal of (bucket, sub-range) items
-  uint32_t item0 = 0;
-  const bool tail = h_first >= MSM_HEAVY_CAP;
-  for (uint32_t h = tail ? h_first + wg : h_first; h < n_heavy; h += tail ? n_wg : 1u) {
-    const uint32_t b = pmode ? ent[4 * h] : heavy[1 + h];
-    const uint32_t cnt = pmode ? (ent[4 * (h + 1) + 3] - ent[4 * h + 3]) * 32u : count[b];
-    const uint32_t beg0 = pmode ? ent[4 * h + 3] * 32u : begin[b];
-    const uint32_t nsplit = tail ? 1u : heavy_nsplit(h, cnt, 4 * npair, item0);  // ~4 points per lane pair before the tree
-    const uint32_t base = item0;  // first pool slot of the bucket's partial sums (see k_accum_heavy)
-    const uint32_t r0 = tail ? 0u : (wg + n_wg - base % n_wg) % n_wg;
-    item0 += nsplit;
-    for (uint32_t r = r0; r < nsplit; r += n_wg) {  // block-uniform
-      uint32_t beg = beg0, end = beg0 + cnt;
-      if (nsplit > 1) {
-        const uint32_t len = (cnt + nsplit - 1) / nsplit;
-        const uint32_t sb = beg + r * len;
-        end = (sb + len < end) ? sb + len : end;
-        beg = sb < end ? sb : end;
-      }
-      XYZZ<Fq2P> acc = XYZZ<Fq2P>::infinity();
-      if (pmode) {
-        for (uint32_t j = beg + pair; j < end; j += npair) acc.add(partial_at(h, j));  // pair-uniform
-      } else {
-        for (uint32_t j = beg + pair; j < end; j += npair) acc.madd(ld_affine_split(bases, sorted[j], comp));  // pair-uniform
-      }
-      acc = pair_tree_sum(acc, sh, pair, npair, comp);
-      if (nsplit == 1) {
-        if (pair == 0) st_xyzz_split(buckets + b, acc, comp);
-      } else {
-        if (pair == 0) {
-          st_xyzz_split(heavy_partial + (size_t)base + r, acc, comp);
-          __threadfence();  // each lane's half of the partial is visible device-wide ...
-        }
-        __syncthreads();  // ... before the ticket is taken
-        if (threadIdx.x == 0) is_last = atomicAdd(ticket + h, 1u) == nsplit - 1 ? 1u : 0u;
-        __syncthreads();
-        if (is_last) {  // block-uniform
-          __threadfence();
-          XYZZ<Fq2P> v = XYZZ<Fq2P>::infinity();
-          for (uint32_t k = pair; k < nsplit; k += npair) v.add(ld_xyzz_split(heavy_partial + (size_t)base + k, comp));  // pair-uniform
-          v = pair_tree_sum(v, sh, pair, npair, comp);
-          if (pair == 0) st_xyzz_split(buckets + b, v, comp);
-          if (threadIdx.x == 0) ticket[h] = 0;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-template <int UNUSED = 0>
-__global__ void __launch_bounds__(64, 2)
-k_accum_redo_g2_split(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __restrict__ begin,
-                      const uint32_t* __restrict__ count, const uint32_t* __restrict__ sorted,
-                      XYZZ<Fq2_28>* __restrict__ buckets, uint32_t* __restrict__ redo, uint32_t* __restrict__ ticket) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  XYZZ<Fq2_28>* sh = reinterpret_cast<XYZZ<Fq2_28>*>(lds_raw);
-  const uint32_t n = redo[0];
-  const uint32_t pair = threadIdx.x >> 1, comp = threadIdx.x & 1u, npair = blockDim.x >> 1;
-  for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {  // block-uniform: a wave (32 lane pairs) per listed bucket
-    const uint32_t b = redo[1 + k];
-    const uint32_t beg = begin[b], end = beg + count[b];
-    XYZZ<Fq2P> acc = XYZZ<Fq2P>::infinity();
-    for (uint32_t j = beg + pair; j < end; j += npair) acc.madd(ld_affine_split(bases, sorted[j], comp));
-    acc = pair_tree_sum(acc, sh, pair, npair, comp);
-    if (pair == 0) st_xyzz_split(buckets + b, acc, comp);
-    __syncthreads();
-  }
-  // every workgroup has read the length by now; the last one to get here clears the list for the slot's next MSM
-  __syncthreads();
-  if (threadIdx.x == 0 && atomicAdd(ticket, 1u) == gridDim.x - 1) {
-    redo[0] = 0;
-    *ticket = 0;
-  }
+  treesum_final_body<LanePair>(stage, nchunk, partial, partial_host);
 }
 
 }  // namespace zkmi

@@ -233,6 +233,10 @@ int32_t zkmi_pairing(const uint8_t g1_affine[96], const uint8_t g2_affine[192], 
  * exponentiation on the host.  out_fq12: the 576 bytes zkmi_pairing writes.  The points must be in the r-order
  * subgroups (the caller's duty here, as for zkmi_pairing; use zkmi_g{1,2}_points_read_dev). n = 0: out = 1. */
 int32_t zkmi_pairing_product_dev(zkmi_ctx* ctx, const void* d_g1, const void* d_g2, uint64_t n, uint8_t out_fq12[576]);
+/* n reduced pairings e(P_i, Q_i), Miller loop AND final exponentiation on the device: d_out_gt = n x 576 B in HBM
+ * (4-byte aligned), each the bytes zkmi_pairing writes; a pair with an infinite member gives 1.  Same input form and
+ * caller's duties as zkmi_pairing_product_dev.  Waits for the results.  n = 0: ZKMI_OK, nothing written. */
+int32_t zkmi_pairing_batch_dev(zkmi_ctx* ctx, const void* d_g1, const void* d_g2, uint64_t n, void* d_out_gt);
 
 /* ---- rows a1-a5, a7: relation + witness ---------------------------------- */
 /* R1CS in CSR form; column 0 is the constant 1, columns [0, n_pub) are the
@@ -498,6 +502,17 @@ int32_t zkmi_vk_free(zkmi_vk* vk);
 int32_t zkmi_groth16_verify_batch(zkmi_ctx* ctx, const zkmi_vk* vk, uint64_t n, const uint8_t* publics,
                                   const uint8_t* proofs, const uint8_t* weights, uint8_t* out_status,
                                   uint64_t* out_first_bad);
+/* Every proof of one key checked by ITS OWN equation e(A_i,B_i) e(-X_i,gamma) e(-C_i,delta) e(-alpha,beta) = 1 on the
+ * device: no weights, no error term, and the same launches whatever the verdicts -- the call for proofs from outside,
+ * where zkmi_groth16_verify_batch is the call for trusted or mostly good input: one exponentiation for all proofs, but a
+ * bisection with one HOST exponentiation per range once something fails.  The points are read as there, X_i is summed
+ * on the device from a window table of the key, ONE launch runs the 3 n + 1 Miller loops (the pair (-alpha, beta) once per
+ * call), and one lane pair per proof multiplies its four values and raises the product to (p^12 - 1)/r: no pairing and
+ * no final exponentiation runs on the host.  Arguments, statuses (ZKMI_PROOF_*), return codes and out_first_bad as
+ * zkmi_groth16_verify_batch; out_status is required (NULL: ZKMI_ERR_BAD_ARG, as a NULL proofs or publics with n > 0,
+ * before anything is launched).  A malformed proof keeps status 1-4.  n = 0: ZKMI_OK. */
+int32_t zkmi_groth16_verify_each(zkmi_ctx* ctx, const zkmi_vk* vk, uint64_t n, const uint8_t* publics,
+                                 const uint8_t* proofs, uint8_t* out_status, uint64_t* out_first_bad);
 
 /* ---- keys in arkworks' CanonicalSerialize layout (drop-in for keys made by ark-groth16) -------- *
  * VerifyingKey = alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | Vec<gamma_abc_g1>;

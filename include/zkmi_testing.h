@@ -44,6 +44,15 @@ int32_t zkmi_selftest_poseidon(int32_t field, uint64_t seed, uint32_t iters, uin
  * instantiated over the HOST field types: conj, final exponentiation, the 576 bytes of zkmi_pairing.  Pins the formulas
  * against pairing.hip's affine loop without a GPU. */
 int32_t zkmi_selftest_miller_formulas(const uint8_t g1_affine[96], const uint8_t g2_affine[192], uint8_t out_fq12[576]);
+/* The final exponentiation the device runs (csrc/pairing_dev.hip final_exp_chain: tower inversion, Frobenius maps, the hard
+ * part as ((x-1)^2/3)(x+p)(x^2+p^2-1) + 1) instantiated over the HOST field types -> out_chain, and the unchanged
+ * square-and-multiply final_exponentiation on the same input -> out_plain; the two must be equal byte for byte.  Neither is
+ * conjugated first.  A coefficient >= p: ZKMI_ERR_NON_CANONICAL; the input 0: ZKMI_ERR_BAD_ARG. */
+int32_t zkmi_selftest_final_exp_formulas(const uint8_t in_fq12[576], uint8_t out_chain[576], uint8_t out_plain[576]);
+/* The last zkmi_groth16_verify_each of this library, in ms: [0] k_public_sum_g1, [1] k_final_exp (HIP events), [2] the
+ * host's build of the key's window table when that call made it (0 when the key already held it).  One global, last
+ * call wins: a measuring aid for single-threaded scripts; the product library records nothing. */
+int32_t zkmi_verify_each_kernel_ms(float out_ms[3]);
 /* Where the last zkmi_groth16_verify_batch of this library spent its time, in ms of host clock, the stream waited for at
  * every boundary (the product library neither waits there nor records): [0] upload and split, [1] decompression and
  * subgroup checks, [2] w_i A_i and the MSM bases, [3] the n Miller loops, [4] the three sums (host Fr, MSM, scalar

@@ -114,6 +114,12 @@ extern "C" {
                                      weights: *const u8, out_status: *mut u8, out_first_bad: *mut u64) -> i32;
     pub fn zkmi_pairing_product_dev(ctx: *mut zkmi_ctx, d_g1: *const core::ffi::c_void, d_g2: *const core::ffi::c_void, n: u64,
                                     out_fq12: *mut u8) -> i32;
+    // every proof by its own equation, final exponentiation on the device: the same work whatever the verdicts (proofs from
+    // outside); out_status is required.  zkmi_pairing_batch_dev: n reduced pairings, n x 576 B written to HBM
+    pub fn zkmi_groth16_verify_each(ctx: *mut zkmi_ctx, vk: *const zkmi_vk, n: u64, publics: *const u8, proofs: *const u8,
+                                    out_status: *mut u8, out_first_bad: *mut u64) -> i32;
+    pub fn zkmi_pairing_batch_dev(ctx: *mut zkmi_ctx, d_g1: *const core::ffi::c_void, d_g2: *const core::ffi::c_void, n: u64,
+                                  d_out_gt: *mut core::ffi::c_void) -> i32;
 
     // the mock's own surface, bit for bit (row a12) — lets call sites migrate one at a time
     pub fn zkmi_account_new(tokens: *const zkmi_scalar, out: *mut zkmi_account) -> i32;

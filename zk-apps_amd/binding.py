@@ -771,6 +771,29 @@ class Context:
             self._chk(rc)
         return rc == 0, (bytes(st)[:n] if want_status else None), (None if bad.value == NO_INDEX else bad.value)
 
+    def pairing_batch_dev(self, d_g1, d_g2, n, d_out):
+        """zkmi_pairing_batch_dev: n reduced pairings e(P_i, Q_i) of pairs in HBM (affine wire form, subgroup points), Miller
+        loop and final exponentiation on the device; d_out receives n x 576 B, each the bytes Zkmi.pairing returns."""
+        self._chk(self.lib.zkmi_pairing_batch_dev(self.h, C.c_void_p(d_g1) if d_g1 else None, C.c_void_p(d_g2) if d_g2 else None,
+                                                  C.c_uint64(n), C.c_void_p(d_out) if d_out else None))
+
+    def groth16_verify_each(self, vk, publics, proofs):
+        """zkmi_groth16_verify_each over host bytes: every proof checked by its own equation on the device, the same work
+        whatever the verdicts (the call for proofs from outside; groth16_verify_batch is the one for trusted input).  vk from
+        Zkmi.vk_prepare, proofs n x 192 B, publics n x (n_pub - 1) x 32 B.  Returns (ok, status bytes, first_bad or None); a
+        rejected batch is a result, not an exception.  Lengths that do not fit the key raise ZkmiError (BAD_ARG) before the
+        library is called; anything else (HIP error) raises ZkmiError too."""
+        n = len(proofs) // 192
+        if len(proofs) != 192 * n or len(publics) != 32 * (vk.n_pub - 1) * n:
+            raise ZkmiError(-1, "groth16_verify_each: %d bytes of proofs and %d of publics do not fit a key with n_pub = %d"
+                            % (len(proofs), len(publics), vk.n_pub))
+        st = (C.c_uint8 * max(1, n))()
+        bad = C.c_uint64(NO_INDEX)
+        rc = self.lib.zkmi_groth16_verify_each(self.h, vk.h, C.c_uint64(n), _buf(publics), _buf(proofs), st, C.byref(bad))
+        if rc not in (0, -2, -5):
+            self._chk(rc)
+        return rc == 0, bytes(st)[:n], (None if bad.value == NO_INDEX else bad.value)
+
     def bases_g1_synthetic_range(self, first, n):
         h = C.c_void_p()
         self._chk(self.z.tlib.zkmi_bases_g1_synthetic_range(self.h, C.c_uint64(first), C.c_uint64(n), C.byref(h)))

@@ -18,4 +18,11 @@ hipError_t miller_values_dev(zkmi_ctx* ctx, const void* d_g1, const void* d_g2, 
 constexpr uint64_t MILLER_PARTIALS = 256;
 int32_t miller_product_dev(zkmi_ctx* ctx, const void* d_miller, uint64_t n, void* d_partials, Fq12* out);
 
+// n >= 1 groups of Miller values -> conj, ^((p^12 - 1)/r) on the device.  Group i is the product of the g values at index
+// i * group_stride + k * member_stride (k < g) of d_miller and, when d_shared is given, of the one value there.  Either
+// d_out_gt (n x MILLER_BYTES: the bytes of zkmi_pairing) or d_out_status (n bytes: ZKMI_PROOF_OK when the result is 1,
+// else ZKMI_PROOF_PAIRING) is written.  Queued on ctx->stream; does not wait.
+hipError_t final_exp_dev(zkmi_ctx* ctx, const void* d_miller, uint64_t n, uint32_t g, uint64_t group_stride,
+                         uint64_t member_stride, const void* d_shared, void* d_out_gt, void* d_out_status);
+
 }  // namespace zkmi

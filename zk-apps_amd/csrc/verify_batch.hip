@@ -19,15 +19,9 @@
 #include <new>
 #include <vector>
 #include "pairing_dev.hpp"
+#include "verify.hpp"
 #include "points.hpp"
 #include "field28.hpp"
-
-struct zkmi_vk {
-  uint32_t n_pub = 0;
-  zkmi::G1Affine alpha;
-  zkmi::G2Affine beta, gamma, delta;
-  std::vector<zkmi::G1Affine> ic;
-};
 
 namespace zkmi {
 

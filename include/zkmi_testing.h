@@ -62,6 +62,38 @@ int32_t zkmi_verify_batch_phases(double out_ms[7]);
  * against curve.hpp's one-lane addition on the device and the 32-bit-limb host arithmetic: n pairs with every special case
  * (o = a, o = -a, either at infinity, equal points in different representations), and 16-point sums over the quads of a wave. */
 int32_t zkmi_selftest_quad_add(zkmi_ctx* ctx, uint64_t seed, uint32_t n, uint32_t* out_mismatches);
+/* One operation of the device limb arithmetic (csrc/field28.hpp) on n tuples of RAW limb arrays: every operand and every
+ * result is NL int32 limbs (14 for field 0, 10 for the others), tuple after tuple, and nothing is converted on the way in or
+ * out, so a caller chooses the representation (x + k p, negative top limb, ...) of every operand.  ctx != NULL: one lane per
+ * tuple on the device; ctx == NULL: the same templated body on the host.  tests/limbs28.py holds the big-integer reference.
+ *   field  0 Fq28 (BLS12-381 base), 1 Fr28 (BLS12-381 scalar), 2 BnFq28, 3 BnFr28
+ *   op     in -> out, in elements per tuple (csrc/field28_selftest.hip):
+ *     0 a b -> a + b            1 a b -> a - b             2 a -> neg            3 a -> dbl
+ *     4 a b -> add_lazy, carry  5 a b -> a * b             6 a -> sqr
+ *     7 a b c d -> add_lazy(a, b) * sub_lazy(c, d)
+ *     8 a b c d e f -> f_mul_sub_mul(a.sub_lazy(b), c.sub_lazy(d), e, f)
+ *     9 a b c -> f_x3(a, b, c) = a - b - 2 c
+ *    10 a b c -> f_signed_sub_lazy(a, 0, b) * c, f_signed_sub_lazy(a, ~0, b) * c
+ *    11 a -> is_zero (one byte per tuple in out_flag; the only op that writes out_flag instead of out)
+ *    12 w -> from_canonical (the canonical 32-bit words in the first N32 slots of an NL-slot element)
+ *    13 a -> to_canonical (words in the first N32 slots, the other slots 0)
+ *    14 a -> inv
+ *   field 0 only, an Fq2 element being the two elements c0, c1:
+ *    15 a b -> a * b    16 a -> sqr    17 a b c d -> f_mul_sub_mul = a b - c d    18 a b c -> f_x3
+ *   field 0 and the device only, an Fq2 element split over a lane pair (Fq2P: even lane c0, odd lane c1):
+ *    19 a b -> a * b    20 a -> sqr    21 a b c d -> f_mul_sub_mul
+ *    22 a b -> f_signed_sub_lazy(a, 0, b), f_signed_sub_lazy(a, ~0, b)
+ *    23 a -> is_zero (two bytes per tuple in out_flag: what the even and what the odd lane saw)
+ *   any field, the host only (the product-scanning forms are an A/B build, not the product):
+ *    24 a b -> mul_fips    25 a -> sqr_fips    26 a b c d -> fipsn<2> = a b + c d    27 a .. h -> fipsn<4> = a b + c d + e f + g h
+ * An op the field or the path does not have: ZKMI_ERR_BAD_ARG. */
+int32_t zkmi_selftest_fp28_ops(zkmi_ctx* ctx, int32_t field, int32_t op, uint32_t n, const int32_t* in, int32_t* out,
+                               uint8_t* out_flag);
+/* The decimation-in-frequency transform of the prover (csrc/ntt.hip inverse_to_rev: natural order in, bit-reversed order out)
+ * alone, on 2^log_n canonical 32-byte scalars in HBM, in place; the public NTT entry points run the decimation-in-time
+ * passes only.  field: 1 BLS12-381 Fr, 3 BN254 Fr (as above).  post 0: position p holds sum_i x_i w^(-i rev(p)), unscaled;
+ * post 1: that times g^rev(p) / N (the table the witness map applies in the last pass, g = 7). */
+int32_t zkmi_selftest_ntt_dif_dev(zkmi_ctx* ctx, int32_t field, void* d_data, uint32_t log_n, int32_t post);
 /* Test hook for the bucket set two MSMs share (the prover's L and H queries): sum_i a_i P_i + sum_i b_i P_i
  * with the first MSM's accumulation left unreduced and the second one's reduction taking both bucket arrays (prepared
  * bases run the shared-bucket schedule, others the windowed one).  Scalars in HBM. */

@@ -475,6 +475,8 @@ int32_t zkmi_bn254_msm_g1(zkmi_ctx* ctx, const uint8_t* scalars, uint64_t n, con
 
 int32_t zkmi_bn254_ntt_fr_dev(zkmi_ctx* ctx, void* d_data, uint32_t log_n, int32_t inverse, int32_t coset) {
   ZK_ENTER(ctx);
+  // log_n <= 26: a DIF sum path reaches 2^log_n times its input's representation and the signed top limb holds 2^29.4 r
+  // (ntt.hip header); measured margin above 2^26: three further doublings (oracle/field28_ubsan.cpp)
   if (!d_data || log_n > 26) return ZKMI_ERR_BAD_ARG;
   hipError_t e;
   NttDomainBn* dom = ctx->domain_bn((int)log_n, &e);

@@ -311,6 +311,8 @@ int32_t zkmi_prof_get(zkmi_ctx* ctx, int32_t phase, double* out_total_ms, uint64
 // ---------------------------------------------------------------------------
 int32_t zkmi_ntt_fr_dev(zkmi_ctx* ctx, void* d_data, uint32_t log_n, int32_t inverse, int32_t coset) {
   ZK_ENTER(ctx);
+  // log_n <= 26: a DIF sum path reaches 2^log_n times its input's representation and the signed top limb holds 2^28.1 r
+  // (ntt.hip header); measured margin above 2^26: two further doublings (oracle/field28_ubsan.cpp)
   if (!ctx || !d_data || log_n > 26) return ZKMI_ERR_BAD_ARG;
   hipError_t e;
   NttDomain* dom = ctx->domain((int)log_n, &e);

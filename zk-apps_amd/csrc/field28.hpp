@@ -482,7 +482,10 @@ ZK_HD Fp28<P> f_x3(const Fp28<P>& rr, const Fp28<P>& ppp, const Fp28<P>& q) {
   r.carry();
   return r;
 }
-// a b - c d under one reduction (a, b may be lazy differences; c, d normalised)
+// a b - c d under one reduction (a, b may be lazy differences; c, d normalised).  Range: with every operand at the
+// |v| < 16 p bound the column sum reaches (32 p)^2 + (16 p)^2 = 1280 p^2, i.e. 0.508 p after the division by R in Fq28,
+// so the result lies in (-p, 2p) -- not in the (-p/2, 3p/2) of a single product; still normalised and within is_zero()'s
+// range.  (The Fq2 form below sums four products of normalised operands: 1024 p^2, inside (-p/2, 3p/2).)
 template <class P>
 ZK_HD Fp28<P> f_mul_sub_mul(const Fp28<P>& a, const Fp28<P>& b, const Fp28<P>& c, const Fp28<P>& d) {
   constexpr int NL = P::NL;

@@ -6,8 +6,16 @@
 //
 // Element type: Fr28 = 10 signed 28-bit limbs (40 B), Montgomery R = 2^280,
 // lazily reduced (field28.hpp): a butterfly is one 270-instruction product
-// plus two carry-swept add/sub; values may grow by ~1.5 r per stage, which the
-// 25 spare bits of the radix absorb, so nothing is reduced between stages.
+// plus two carry-swept add/sub, and nothing is reduced between stages.  Growth:
+//   DIT: y = tile[L1] * w is a fresh product in [0, r], so x + y and x - y grow by about r per stage (26 r at N = 2^26).
+//   DIF: tile[L0] = x + y sums two unreduced values: the sum path DOUBLES every stage, and only the difference path is
+//        pulled back by its product.  Plans of one or two passes twist (multiply) every element between the passes;
+//        three-pass plans (N > 2^20) do not, so entry 0 of a constant vector reaches N times its representation, and
+//        the last stage takes the lazy difference of two values of N/2 times theirs.  What bounds N is the signed
+//        32-bit top limb (2^252 units): |v| < 2^31 2^252 = 2^28.1 r (BLS12-381) or 2^29.4 r (BN254).  With inputs in
+//        [0, r] -- from_canonical() and every product give that -- N = 2^26 leaves two (BN254: three) further
+//        doublings: oracle/field28_ubsan.cpp measures it, tests/test_gpu_field28.py runs the constant and the
+//        alternating vector at 2^26.  An input that is itself a sum of k such values has log2 k bits less.
 //
 // Kernel plan (LDS-staged butterflies).  A pass owns up to 10 consecutive
 // butterfly stages: every workgroup stages a tile of 2^S x 2^Q elements in LDS

@@ -18,14 +18,24 @@ struct Rng {
     return z ^ (z >> 31);
   }
   Fq fq() {
-    Fq a;
-    for (int i = 0; i < 12; i += 2) {
-      uint64_t v = next();
-      a.l[i] = (uint32_t)v;
-      a.l[i + 1] = (uint32_t)(v >> 32);
+    // uniform over [0, p) up to the bias of the top word's reduction: the top word modulo its largest value + 1, and a
+    // draw that still is >= p (top word equal to p's, the rest not below) is rejected
+    for (;;) {
+      Fq a;
+      for (int i = 0; i < 12; i += 2) {
+        uint64_t v = next();
+        a.l[i] = (uint32_t)v;
+        a.l[i + 1] = (uint32_t)(v >> 32);
+      }
+      a.l[11] %= FqParams::MOD[11] + 1u;
+      bool below = false;
+      for (int i = 11; i >= 0; i--)
+        if (a.l[i] != FqParams::MOD[i]) {
+          below = a.l[i] < FqParams::MOD[i];
+          break;
+        }
+      if (below) return a;  // arbitrary residue, read as Montgomery form
     }
-    a.l[11] &= 0x0fffffffu;  // < 2^380 < p
-    return a;                // arbitrary residue, read as Montgomery form
   }
 };
 }  // namespace

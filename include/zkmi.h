@@ -576,6 +576,40 @@ int32_t zkmi_ark_pk_load_validated(zkmi_ctx* ctx, const zkmi_r1cs* r1cs, const u
  * elements (section 5: alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2) on the host.  checks must not be 0. */
 int32_t zkmi_pk_check(zkmi_ctx* ctx, const zkmi_pk* pk, int32_t checks, uint64_t out_where[2]);
 
+/* ---- phase-1 transcripts ("powers of tau" with alpha and beta) and transforms of point arrays ------------------- *
+ * The first layers of a setup that never sees the toxic waste: a ceremony transcript -- the five point arrays
+ * [tau^i]G1, [tau^i]G2, [alpha tau^i]G1, [beta tau^i]G1, [beta]G2 -- resident and checked on the device, and the
+ * transform that turns powers of tau into the Lagrange basis [L_i(tau)]G "in the exponent".  Deriving a relation's
+ * key from them (the sums over the R1CS columns, the delta contribution) is not in the library yet:
+ * zkmi_groth16_setup, with explicit toxic waste, stays the only setup. */
+/* In-place transform of 2^log_n points in HBM, affine WIRE form (all zero = infinity), natural order in and out:
+ * out[i] = sum_k w^(ik) in[k] (forward), out[i] = N^-1 sum_k w^(-ik) in[k] (inverse), w = the root zkmi_ntt_fr uses.
+ * The points must be in the r-order subgroup (caller's duty, as for zkmi_pairing_product_dev); a coordinate >= p is
+ * refused (ZKMI_ERR_NON_CANONICAL, nothing written).  log_n 0..26.  Waits for the result. */
+int32_t zkmi_g1_points_ntt_dev(zkmi_ctx* ctx, void* d_points, uint32_t log_n, int32_t inverse);
+int32_t zkmi_g2_points_ntt_dev(zkmi_ctx* ctx, void* d_points, uint32_t log_n, int32_t inverse);
+typedef struct zkmi_srs zkmi_srs;
+/* Phase-1 transcript from host bytes in any ZKMI_ENC_* encoding, parsed / decompressed / checked on the device
+ * under `checks` (ZKMI_CHECK_*), exactly as zkmi_bases_g{1,2}_load_encoded does:
+ *   tau_g1 n_tau_g1 points [tau^i]G1, tau_g2 n_tau_g2 points [tau^i]G2, alpha_tau_g1 / beta_tau_g1 n_ab points each,
+ *   beta_g2 one point.  Also refused (ZKMI_ERR_NON_CANONICAL): tau_g1[0] != G1 generator, tau_g2[0] != G2 generator.
+ * out_where (optional): [0] = section of the refused point (0 tau_g1, 1 tau_g2, 2 alpha_tau_g1, 3 beta_tau_g1,
+ * 4 beta_g2), [1] = index; UINT64_MAX twice when no point was refused.  A refused transcript leaves *out NULL.
+ * NOT checked: that the arrays are consistent powers of ONE tau, alpha and beta -- the pairing "same ratio" checks of a
+ * ceremony verifier.  A transcript that fails those yields a key that proves nothing; verify it before it gets here. */
+int32_t zkmi_srs_load(zkmi_ctx* ctx, int32_t encoding, int32_t checks,
+                      const uint8_t* tau_g1, uint64_t n_tau_g1, const uint8_t* tau_g2, uint64_t n_tau_g2,
+                      const uint8_t* alpha_tau_g1, const uint8_t* beta_tau_g1, uint64_t n_ab,
+                      const uint8_t* beta_g2, zkmi_srs** out, uint64_t out_where[2]);
+/* The same transcript from explicit toxic waste tau|alpha|beta (3 x 32 B), for a domain of 2^log_n: 2^(log_n+1) - 1
+ * powers in tau_g1, 2^log_n in the others; fixed-base multiplications on the device.  Tests and benches only,
+ * like zkmi_groth16_setup.  log_n 0..26. */
+int32_t zkmi_srs_generate(zkmi_ctx* ctx, const uint8_t toxic[96], uint32_t log_n, zkmi_srs** out);
+int32_t zkmi_srs_shape(const zkmi_srs* s, uint64_t out[3]);          /* n_tau_g1, n_tau_g2, n_ab */
+/* count points of a section (numbered as in out_where above) from `first`, affine WIRE form (96 / 192 B each) */
+int32_t zkmi_srs_read(zkmi_ctx* ctx, const zkmi_srs* s, int32_t section, uint64_t first, uint64_t count, uint8_t* out_wire);
+int32_t zkmi_srs_free(zkmi_srs* s);
+
 /* ---- row a12: the reference's prove/verify surface ------------------------ */
 #define ZKMI_MERKLE_TREE_DEPTH 10 /* shielder/mocked_zk/src/lib.rs:16 */
 #define ZKMI_TOKENS_NUMBER 2      /* shielder/mocked_zk/src/lib.rs:17 */

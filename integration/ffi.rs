@@ -25,6 +25,7 @@ pub const ZKMI_MAX_TREE_HEIGHT: usize = 32;
 #[repr(C)] pub struct zkmi_bases_g2 { _p: [u8; 0] }
 #[repr(C)] pub struct zkmi_comm { _p: [u8; 0] }
 #[repr(C)] pub struct zkmi_vk { _p: [u8; 0] }
+#[repr(C)] pub struct zkmi_srs { _p: [u8; 0] }
 
 /// = `Scalar { bytes: [u8; 32] }` (mocked_zk/src/scalar.rs:1-6), little-endian
 #[repr(C)] #[derive(Clone, Copy)] pub struct zkmi_scalar { pub bytes: [u8; 32] }
@@ -89,6 +90,16 @@ extern "C" {
     pub fn zkmi_ark_pk_load_validated(ctx: *mut zkmi_ctx, r1cs: *const zkmi_r1cs, buf: *const u8, len: u64, compressed: i32, checks: i32,
                                       out_pk: *mut *mut zkmi_pk, out_vk: *mut u8, vk_cap: u64, out_where: *mut u64) -> i32;
     pub fn zkmi_pk_check(ctx: *mut zkmi_ctx, pk: *const zkmi_pk, checks: i32, out_where: *mut u64) -> i32;
+    // phase-1 transcripts (powers of tau with alpha and beta) and transforms of point arrays on the device
+    pub fn zkmi_g1_points_ntt_dev(ctx: *mut zkmi_ctx, d_points: *mut core::ffi::c_void, log_n: u32, inverse: i32) -> i32;
+    pub fn zkmi_g2_points_ntt_dev(ctx: *mut zkmi_ctx, d_points: *mut core::ffi::c_void, log_n: u32, inverse: i32) -> i32;
+    pub fn zkmi_srs_load(ctx: *mut zkmi_ctx, encoding: i32, checks: i32, tau_g1: *const u8, n_tau_g1: u64, tau_g2: *const u8, n_tau_g2: u64,
+                         alpha_tau_g1: *const u8, beta_tau_g1: *const u8, n_ab: u64, beta_g2: *const u8, out: *mut *mut zkmi_srs,
+                         out_where: *mut u64) -> i32;
+    pub fn zkmi_srs_generate(ctx: *mut zkmi_ctx, toxic: *const u8, log_n: u32, out: *mut *mut zkmi_srs) -> i32;
+    pub fn zkmi_srs_shape(s: *const zkmi_srs, out: *mut u64) -> i32;
+    pub fn zkmi_srs_read(ctx: *mut zkmi_ctx, s: *const zkmi_srs, section: i32, first: u64, count: u64, out_wire: *mut u8) -> i32;
+    pub fn zkmi_srs_free(s: *mut zkmi_srs) -> i32;
     pub fn zkmi_ark_vk_read(buf: *const u8, len: u64, compressed: i32, out_vk: *mut u8, vk_cap: u64, out_n_pub: *mut u32, out_consumed: *mut u64) -> i32;
     pub fn zkmi_pk_shape(pk: *const zkmi_pk, n_vars: *mut u32, n_pub: *mut u32, log_n: *mut u32) -> i32;
     pub fn zkmi_host_info(out: *mut u32) -> i32;

@@ -995,6 +995,39 @@ class Context:
         self._chk(self.lib.zkmi_groth16_setup(self.h, r1cs.h, _buf(toxic), C.byref(h), vk, C.c_uint64(cap)))
         return ProvingKey(self, h, r1cs), bytes(vk)
 
+    def g1_points_ntt_dev(self, d_points, log_n, inverse=False):
+        """zkmi_g1_points_ntt_dev: 2^log_n G1 points at device address d_points (affine wire form, subgroup points)
+        transformed in place, natural order in and out; the inverse is scaled by N^-1."""
+        self._chk(self.lib.zkmi_g1_points_ntt_dev(self.h, C.c_void_p(d_points) if d_points else None, C.c_uint32(log_n), C.c_int32(int(inverse))))
+
+    def g2_points_ntt_dev(self, d_points, log_n, inverse=False):
+        self._chk(self.lib.zkmi_g2_points_ntt_dev(self.h, C.c_void_p(d_points) if d_points else None, C.c_uint32(log_n), C.c_int32(int(inverse))))
+
+    def srs_load(self, encoding, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, checks=CHECK_SUBGROUP):
+        """Phase-1 transcript from host bytes in any ENC_* form, every point parsed and checked on the device under `checks`.
+        A refused transcript raises ZkmiError (NON_CANONICAL) whose `where` is (section, index) of the refused point
+        (sections: 0 tau_g1, 1 tau_g2, 2 alpha_tau_g1, 3 beta_tau_g1, 4 beta_g2), or None."""
+        w1 = 96 // (2 if encoding == ENC_ZCASH_COMPRESSED else 1)
+        assert len(alpha_tau_g1) == len(beta_tau_g1) and len(beta_g2) == 2 * w1
+        h = C.c_void_p()
+        where = (C.c_uint64 * 2)(NO_INDEX, NO_INDEX)
+        rc = self.lib.zkmi_srs_load(self.h, C.c_int32(encoding), C.c_int32(checks), _buf(tau_g1), C.c_uint64(len(tau_g1) // w1),
+                                    _buf(tau_g2), C.c_uint64(len(tau_g2) // (2 * w1)), _buf(alpha_tau_g1), _buf(beta_tau_g1),
+                                    C.c_uint64(len(alpha_tau_g1) // w1), _buf(beta_g2), C.byref(h), where)
+        if rc != 0:
+            err = ZkmiError(rc, (self.lib.zkmi_last_error(self.h) or b"").decode())
+            err.where = None if where[0] == NO_INDEX else (int(where[0]), int(where[1]))
+            assert not h.value
+            raise err
+        return Srs(self, h)
+
+    def srs_generate(self, toxic, log_n):
+        """The transcript of explicit toxic waste tau|alpha|beta (96 bytes) for a domain of 2^log_n: tests and benches only."""
+        assert len(toxic) == 96
+        h = C.c_void_p()
+        self._chk(self.lib.zkmi_srs_generate(self.h, _buf(toxic), C.c_uint32(log_n), C.byref(h)))
+        return Srs(self, h)
+
     def pk_load(self, r1cs, alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2, a_q, b1_q, b2_q, h_q, l_q):
         h = C.c_void_p()
         self._chk(
@@ -1133,6 +1166,29 @@ class Bases:
         if self.h:
             fn = self.ctx.lib.zkmi_bases_g1_free if self.group == 1 else self.ctx.lib.zkmi_bases_g2_free
             fn(self.h)
+            self.h = None
+
+
+class Srs:
+    """A resident phase-1 transcript (zkmi_srs): sections 0 tau_g1, 1 tau_g2, 2 alpha_tau_g1, 3 beta_tau_g1, 4 beta_g2."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def shape(self):
+        out = (C.c_uint64 * 3)()
+        self.ctx._chk(self.ctx.lib.zkmi_srs_shape(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def read(self, section, first, count):
+        w = 192 if section in (1, 4) else 96
+        out = (C.c_uint8 * (w * max(1, count)))()
+        self.ctx._chk(self.ctx.lib.zkmi_srs_read(self.ctx.h, self.h, C.c_int32(section), C.c_uint64(first), C.c_uint64(count), out))
+        return bytes(out)[: w * count]
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.zkmi_srs_free(self.h)
             self.h = None
 
 

@@ -34,6 +34,7 @@
 #include "pairing.hpp"
 #include "r1cs.hpp"
 #include "points.hpp"
+#include "points_ntt.hpp"
 
 namespace zkmi {
 
@@ -526,8 +527,9 @@ static void fr_limbs(const Fr& mont, uint32_t k[8]) {
   memcpy(k, c.l, 32);
 }
 
+namespace zkmi {
 template <class F>
-static hipError_t fixed_base_table(const Affine<F>& base, Affine<F>** d_table) {
+hipError_t fixed_base_table(const Affine<F>& base, Affine<F>** d_table) {
   std::vector<Affine<F>> t(32 * 256);
   XYZZ<F> wbase = XYZZ<F>::from_affine(base);
   for (int w = 0; w < 32; w++) {
@@ -546,8 +548,7 @@ static hipError_t fixed_base_table(const Affine<F>& base, Affine<F>** d_table) {
 
 // out[i] = scalars[i] * base for Montgomery-form host scalars
 template <class F>
-static hipError_t fixed_base_batch(zkmi_ctx* ctx, const Affine<F>* d_table, const std::vector<Fr>& scalars_mont,
-                                   Affine<F>* d_out) {
+hipError_t fixed_base_batch(zkmi_ctx* ctx, const Affine<F>* d_table, const std::vector<Fr>& scalars_mont, Affine<F>* d_out) {
   const size_t n = scalars_mont.size();
   if (!n) return hipSuccess;
   std::vector<Fr> canon(n);
@@ -560,6 +561,12 @@ static hipError_t fixed_base_batch(zkmi_ctx* ctx, const Affine<F>* d_table, cons
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return hipStreamSynchronize(ctx->stream);
 }
+// points_ntt.hip (zkmi_srs_generate) runs the same tables
+template hipError_t fixed_base_table<Fq>(const G1Affine&, G1Affine**);
+template hipError_t fixed_base_table<Fq2>(const G2Affine&, G2Affine**);
+template hipError_t fixed_base_batch<Fq>(zkmi_ctx*, const G1Affine*, const std::vector<Fr>&, G1Affine*);
+template hipError_t fixed_base_batch<Fq2>(zkmi_ctx*, const G2Affine*, const std::vector<Fr>&, G2Affine*);
+}  // namespace zkmi
 
 uint64_t zkmi_layout_pk() { return sizeof(zkmi_pk); }  // capi.hip zkmi_abi_layout_probe
 

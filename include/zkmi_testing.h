@@ -89,6 +89,44 @@ int32_t zkmi_selftest_quad_add(zkmi_ctx* ctx, uint64_t seed, uint32_t n, uint32_
  * An op the field or the path does not have: ZKMI_ERR_BAD_ARG. */
 int32_t zkmi_selftest_fp28_ops(zkmi_ctx* ctx, int32_t field, int32_t op, uint32_t n, const int32_t* in, int32_t* out,
                                uint8_t* out_flag);
+/* One operation of the device pairing tower (csrc/pairing_dev.hip) on n tuples of RAW limb arrays, in the convention of the
+ * call above: every Fq element is 14 int32 limbs, an Fq2 element is c0 then c1, an Fq12 value its six Fq2 coefficients in the
+ * order of e12_load (c0.a0 c0.a1 c0.a2 c1.a0 c1.a1 c1.a2); nothing is converted, the caller chooses the representation
+ * x + k p of every operand.  ctx != NULL: one tuple per LANE PAIR over Fq2P with the launch of the product's kernels (64
+ * lanes per block, tail pairs shadow the last tuple and write nothing); ctx == NULL: the same templated bodies on the host
+ * over Fq2_28.  tests/tower28.py holds the big-integer reference.  n <= 65536.
+ *   op   operands -> results, in Fq elements per tuple (csrc/pairing_dev_selftest.hpp):
+ *     0 shrink              a (Fq) -> a - k p                          1 -> 1
+ *     1 e2_mul_xi  2 e2_conj  3 e2_inv        a -> .                   2 -> 2
+ *     4 e6_mul              a b -> a b                                 12 -> 6
+ *     5 e12_sqr             a -> a^2                                   12 -> 12
+ *     6 e12_mul             a b -> a b                                 24 -> 12
+ *     7 e12_mul_line        f l0 l1 l2 -> f (l0 + (l1 v + l2 v^2) w)   18 -> 12
+ *     8 e12_conj  9 e12_frob_p  10 e12_frob_p2    a -> .               12 -> 12
+ *    11 e6_inv              a -> 1/a (0 -> 0)                          6 -> 6
+ *    12 e12_inv             a -> 1/a (0 -> 0)                          12 -> 12
+ *    13 step_tangent        T = (x y z), xP, -yP -> T', l0 l1 l2       8 -> 12
+ *    14 step_chord          T, xQ yQ, xP, -yP -> T', l0 l1 l2          12 -> 12
+ *    15 miller_rounds       xQ yQ, xP, -yP -> f                        6 -> 12
+ *    16 final_exp_chain     f -> f^((p^12 - 1)/r)                      12 -> 12
+ *    17 words_round_trip    a (Fq) -> the 12 canonical words of limbs_to_words in the first 12 slots of an element (the
+ *                           other two 0), then limbs_from_words of those words                          1 -> 2
+ *    18 is_one              f -> one byte per tuple in out_flag: the status expression of k_final_exp    12 -> 0
+ * An op out of range: ZKMI_ERR_BAD_ARG. */
+int32_t zkmi_selftest_tower_ops(zkmi_ctx* ctx, int32_t op, uint32_t n, const int32_t* in, int32_t* out, uint8_t* out_flag);
+/* The same tower templates over an INTERVAL type, on the host: every Fq2 value is a closed interval in units of p, sums
+ * propagate it, a product records its operands and returns the (-1/2, 3/2) a Montgomery product promises, shrink records its
+ * input and returns (-2, 2).  Runs the Miller loop from the kernels' entry conditions, e12_mul of two shrunk values, e12_conj
+ * and the final exponentiation chain, and the status expression.
+ *   out_sites[6]: the maximum seen of  [0] |operand| of a product  [1] sum of |a| |b| over the partial products of one
+ *     reduction (p^2)  [2] log2 of the bound on a 64-bit column  [3] |input| of shrink  [4] |input| of is_zero
+ *     [5] |any value held in limbs|
+ *   out_classes[2 x 15]: lo, hi of  0 coefficient of f   1 x, y of T   2 z of T   3 xQ, yQ   4 xP, -yP   5 6 7 l0 l1 l2
+ *     8 coefficient of an e6_mul operand   9 of an e6_inv operand   10 11 12 operand of e2_mul_xi, e2_conj, e2_inv
+ *     13 operand of shrink   14 operand of limbs_to_words
+ * tests/test_cpu_tower.py asserts the maxima against the limits DESIGN.md 5.6.1 derives; the vectors of the tower tests
+ * put every operand at the ends of its class. */
+int32_t zkmi_selftest_tower_bounds(double* out_sites, uint32_t n_sites, double* out_classes, uint32_t n_classes);
 /* The decimation-in-frequency transform of the prover (csrc/ntt.hip inverse_to_rev: natural order in, bit-reversed order out)
  * alone, on 2^log_n canonical 32-byte scalars in HBM, in place; the public NTT entry points run the decimation-in-time
  * passes only.  field: 1 BLS12-381 Fr, 3 BN254 Fr (as above).  post 0: position p holds sum_i x_i w^(-i rev(p)), unscaled;

@@ -10,6 +10,7 @@ import pytest
 import points_corpus as pc
 from conftest import golden
 from oracle import bls12_381 as ec
+from tower28 import _tower_to_poly
 
 pytestmark = pytest.mark.gpu
 
@@ -26,25 +27,6 @@ def _dev(b):
     t = torch.frombuffer(bytearray(b), dtype=torch.uint8).cuda()
     torch.cuda.synchronize()
     return t
-
-
-def _tower_to_poly(gt):
-    """The 576 bytes of zkmi_pairing -> the oracle's Fq[w]/(w^12 - 2w^6 + 2): u = w^6 - 1, v = w^2."""
-    co = [int.from_bytes(gt[48 * i : 48 * i + 48], "little") for i in range(12)]
-    poly = [0] * 12
-    idx = 0
-    for i in range(2):
-        for j in range(3):
-            for u in range(2):
-                c = co[idx]
-                idx += 1
-                e = 2 * j + i
-                if u == 0:
-                    poly[e] = (poly[e] + c) % ec.P
-                else:
-                    poly[e + 6] = (poly[e + 6] + c) % ec.P
-                    poly[e] = (poly[e] - c) % ec.P
-    return poly
 
 
 # ---- pairing batch --------------------------------------------------------------------------------------------------
@@ -101,6 +83,35 @@ def test_pairing_batch_across_a_wave(ctx, zk, pairs33):
     # bilinearity across the wave boundary: e(a G1, b G2) = e(a b G1, G2) != e((a b + 1) G1, G2)
     assert got[0] == got[32] and got[0] != got[31] and got[0] != ONE
     assert len(set(got)) == 33 - 2  # {0, 32} and {5, 6} coincide, nothing else does
+
+
+def test_pairing_batch_of_negated_points(ctx, zk):
+    """(P, Q), (-P, Q), (P, -Q), (-P, -Q): in the oracle's arithmetic the first is the inverse of the second and of the third
+    and equal to the fourth, so the four outputs multiply to one; none of them is one."""
+    rnd = random.Random(47)
+    p, q = ec.g1_mul(rnd.randrange(1, ec.R)), ec.g2_mul(rnd.randrange(1, ec.R))
+    np_, nq = ec.pt_neg(ec.Fq, p), ec.pt_neg(ec.Fq2, q)
+    got, rest = _pairings(ctx, [(p, q), (np_, q), (p, nq), (np_, nq)])
+    assert rest == b""
+    e = [_tower_to_poly(g) for g in got]
+    one = ec.f12_one()
+    assert e[0] == ec.pairing(p, q) and e[0] != one
+    assert ec.f12_mul(e[0], e[1]) == one and ec.f12_mul(e[0], e[2]) == one and e[1] == e[2] and e[3] == e[0]
+    assert e[1] == ec.f12_inv(e[0])
+    acc = one
+    for x in e:
+        acc = ec.f12_mul(acc, x)
+    assert acc == one
+    assert got[1] == zk.pairing(ec.g1_to_bytes(np_), ec.g2_to_bytes(q))
+
+
+def test_pairing_batch_of_one_pair_32_times(ctx, zk):
+    """A whole wave of lane pairs on the same operands: 32 equal outputs, the host's bytes."""
+    rnd = random.Random(48)
+    p, q = ec.g1_mul(rnd.randrange(1, ec.R)), ec.g2_mul(rnd.randrange(1, ec.R))
+    got, rest = _pairings(ctx, [(p, q)] * 32, room=33)
+    assert rest == bytes([CANARY]) * 576
+    assert set(got) == {zk.pairing(ec.g1_to_bytes(p), ec.g2_to_bytes(q))}
 
 
 def test_pairing_batch_of_none_writes_nothing(ctx):
@@ -211,6 +222,41 @@ def test_public_sums_with_a_crafted_key(ctx, zk):
     pubs5 = publics[:4] + [publics[4][:32] + ec.R.to_bytes(32, "little") + publics[4][64:]]
     any5 = [proof(rnd.randrange(ec.R), 3) for _ in range(5)]
     _check_against_host(ctx, zk, vk, pv, pubs5, any5, want=bytes([5, 5, 5, 5, 4]))
+    pv.free()
+
+
+def test_a_product_that_is_one_because_two_members_cancel(ctx, zk):
+    """The status path (f == 1 on the device) where e(A, B) alone equals e(alpha, beta) and the members of X and of C are
+    each other's inverses: C = c G with c = -x gamma / delta, A = alpha beta G.  Accepted, as the host verifier accepts it;
+    with any other c for the same A it is rejected; and with x gamma + c delta = 0 reached through A = -alpha beta G, B = -G2
+    (both remaining members negated) it is accepted again."""
+    gd = golden("groth16_n128.json")
+    vk0 = H(gd["vk"])
+    tox = H(gd["toxic"])
+    _, alpha, beta, gamma, delta = (int.from_bytes(tox[32 * k : 32 * k + 32], "little") for k in range(5))
+    n_pub = (len(vk0) - 672) // 96
+    rnd = random.Random(56)
+    ks = [rnd.randrange(1, ec.R) for _ in range(n_pub)]
+    vk = vk0[:672] + b"".join(ec.g1_to_bytes(ec.g1_mul(k)) for k in ks)
+    pv = zk.vk_prepare(vk)
+    g2 = zk.g2_compress(ec.g2_to_bytes(ec.G2))
+    ng2 = zk.g2_compress(ec.g2_to_bytes(ec.pt_neg(ec.Fq2, ec.G2)))
+    g1c = lambda k: zk.g1_compress(ec.g1_to_bytes(ec.g1_mul(k % ec.R)))
+    publics, proofs, want = [], [], []
+    for i in range(33):  # past one wave of lane pairs
+        row = [rnd.randrange(ec.R) for _ in range(n_pub - 1)]
+        x = (ks[0] + sum(p * k for p, k in zip(row, ks[1:]))) % ec.R
+        c = (-x * gamma * pow(delta, -1, ec.R)) % ec.R
+        assert x and c and (x * gamma + c * delta) % ec.R == 0
+        publics.append(b"".join(p.to_bytes(32, "little") for p in row))
+        kind = i % 3
+        if kind == 0:
+            proofs.append(g1c(alpha * beta) + g2 + g1c(c)), want.append(0)
+        elif kind == 1:
+            proofs.append(g1c(alpha * beta) + g2 + g1c(c + 1)), want.append(5)
+        else:
+            proofs.append(g1c(-alpha * beta) + ng2 + g1c(c)), want.append(0)
+    _check_against_host(ctx, zk, vk, pv, publics, proofs, want=bytes(want), host_on=(0, 1, 2, 31, 32))
     pv.free()
 
 

@@ -13,10 +13,16 @@
 // 3-instruction-per-limb carry sweep.
 //
 // Invariants ("normalised"): limbs 0..12 in [0, 2^28); limb 13 signed and
-// small; the represented integer v = sum l[i] 2^(28 i) satisfies |v| < 16 p.
+// small; the represented integer v = sum l[i] 2^(28 i) satisfies |v| < 16 p
+// in the MSM and NTT code (tests/limbs28.py pins every operation there).
 // Values are NOT reduced to [0, p): a residue has several representations.
 //   * mul/sqr accept any normalised operands (also one lazy add/sub of two
-//     normalised values) and return v in (-p/2, 3p/2).
+//     normalised values) and return v in (-p/2, 3p/2).  The exact condition
+//     is on the column sum, not on one operand: the sum over the partial
+//     products of one reduction of |a||b| must stay below R p / 2 (for Fq28
+//     1260 p^2; two lazy sums of 16 p values reach 1024 p^2).  The pairing
+//     tower (tower_dev.hpp) works to that condition with operands up to
+//     22.5 p and sums up to 202.5 p^2.
 //   * is_zero() is exact for |v| <= 4p, which covers products, Fq2 products and
 //     canonical inputs — the only places it is called (see curve.hpp).
 //   * to_canonical() returns the unique representative in [0, p).

@@ -132,6 +132,28 @@ int32_t zkmi_selftest_tower_bounds(double* out_sites, uint32_t n_sites, double* 
  * passes only.  field: 1 BLS12-381 Fr, 3 BN254 Fr (as above).  post 0: position p holds sum_i x_i w^(-i rev(p)), unscaled;
  * post 1: that times g^rev(p) / N (the table the witness map applies in the last pass, g = 7). */
 int32_t zkmi_selftest_ntt_dif_dev(zkmi_ctx* ctx, int32_t field, void* d_data, uint32_t log_n, int32_t post);
+/* The same transform on 2^log_n RAW 10-limb elements (40 bytes each) in HBM, in place, limbs out: nothing is converted, so the
+ * caller chooses the representation x + k r of every input -- the witness map hands this transform unreduced mat-vec sums.
+ * tests/witness28.py says which inputs the limbs can carry through it. */
+int32_t zkmi_selftest_ntt_dif_raw_dev(zkmi_ctx* ctx, int32_t field, void* d_limbs, uint32_t log_n, int32_t post);
+/* The witness map's contract on value ranges (csrc/witness_bound.hpp; tests/witness28.py is the big-integer
+ * model).  witness_bound: the verdict a key build reaches from the shape alone (host only; rowptr_*: n_constraints + 1
+ * entries) -- bit m of *out_mask: the mat-vec of matrix m (A, B, C) normalises its row sums; out_bound[m]: the worst-case
+ * coherent sum of the first inverse transform of matrix m, in units of r.
+ * pk_normalise: the mask a key carries -> *out_mask (may be NULL); force_mask >= 0 replaces it first (to run the normalised
+ * kernels on a small key), < 0 leaves it.
+ * matvec_dev: the key's mat-vec alone, launched as the witness map launches it, on the assignment d_z (n_vars canonical
+ * 32-byte scalars in HBM).  form 0: one lane per row (k_matvec<1>), 1: eight (k_matvec<8>); k_matvec_long takes the listed
+ * rows behind either.  out_limbs (host): the 3 x 2^log_n raw 10-limb elements a, b, c.
+ * witness_map_stages: the witness map of one proof, stage by stage; out_max[3 s + m] = the largest |top limb| (units of
+ * 2^252) over vector m (a, b, c) behind stage s:  0 z in limb form (one vector, in all three slots)  1 the mat-vec
+ * 2 the inverse transforms and their post products  3 the forward transforms (a, b)  4 k_quotient (a <- a b, c <- N c)
+ * 5 the last transform without its epilogue (a: the x of (x - sub) post). */
+int32_t zkmi_selftest_witness_bound(uint32_t log_n, uint32_t n_pub, uint32_t n_constraints, const uint32_t* rowptr_a,
+                                    const uint32_t* rowptr_b, const uint32_t* rowptr_c, uint32_t* out_mask, double out_bound[3]);
+int32_t zkmi_selftest_pk_normalise(zkmi_pk* pk, int32_t force_mask, uint32_t* out_mask);
+int32_t zkmi_selftest_matvec_dev(zkmi_ctx* ctx, const zkmi_pk* pk, const void* d_z, int32_t form, int32_t* out_limbs);
+int32_t zkmi_selftest_witness_map_stages(zkmi_ctx* ctx, const zkmi_pk* pk, const void* d_z, uint32_t out_max[18]);
 /* Test hook for the bucket set two MSMs share (the prover's L and H queries): sum_i a_i P_i + sum_i b_i P_i
  * with the first MSM's accumulation left unreduced and the second one's reduction taking both bucket arrays (prepared
  * bases run the shared-bucket schedule, others the windowed one).  Scalars in HBM. */

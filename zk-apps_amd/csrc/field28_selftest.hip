@@ -245,4 +245,22 @@ extern "C" int32_t zkmi_selftest_ntt_dif_dev(zkmi_ctx* ctx, int32_t field, void*
   if (!dom) return ctx->hip_fail(e, "bn254 ntt domain init");
   return ntt_dif<BnFr28>(ctx, dom, d_data, log_n, post);
 }
+
+// the same transform on RAW limbs, in place: what the witness map hands it (unreduced mat-vec sums) is the caller's to choose
+extern "C" int32_t zkmi_selftest_ntt_dif_raw_dev(zkmi_ctx* ctx, int32_t field, void* d_limbs, uint32_t log_n, int32_t post) {
+  ZK_ENTER(ctx);
+  if (!d_limbs || log_n == 0 || log_n > 26 || (field != 1 && field != 3)) return ZKMI_ERR_BAD_ARG;
+  hipError_t e;
+  if (field == 1) {
+    NttDomain* dom = ctx->domain((int)log_n, &e);
+    if (!dom) return ctx->hip_fail(e, "ntt domain init");
+    ZK_HIP(ctx, dom->inverse_to_rev(static_cast<Fr28*>(d_limbs), post ? dom->rev_coset_n : nullptr, nullptr, ctx->stream));
+  } else {
+    NttDomainBn* dom = ctx->domain_bn((int)log_n, &e);
+    if (!dom) return ctx->hip_fail(e, "bn254 ntt domain init");
+    ZK_HIP(ctx, dom->inverse_to_rev(static_cast<BnFr28*>(d_limbs), post ? dom->rev_coset_n : nullptr, nullptr, ctx->stream));
+  }
+  ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ZKMI_OK;
+}
 #endif  // ZKMI_TESTING

@@ -35,6 +35,7 @@
 #include "r1cs.hpp"
 #include "points.hpp"
 #include "points_ntt.hpp"
+#include "witness_bound.hpp"
 
 namespace zkmi {
 
@@ -72,7 +73,11 @@ struct MatSet {
 // would keep one lane busy for a second while the chip waits: the rows of a relation are as long as its author made them).
 // The key lists such rows at setup (normally none, and then nothing is launched); k_matvec leaves them to k_matvec_long:
 // one 256-thread workgroup per (listed row, proof of the group), terms dealt round-robin, partial sums added through LDS.
+// NORM (both kernels): bit m set = matrix m is NORMALISED -- its row sums are multiplied by one() before they are stored, which
+// brings them from 3/2 k r back into (-r/2, 3r/2).  The key decides it from the relation's shape (witness_bound.hpp, DESIGN.md
+// 5.3); NORM = 0, every key whose coherent sums fit the limbs, is the code without it.
 constexpr uint32_t MATVEC_LONG_ROW = 1024;
+template <int NORM>
 __global__ void __launch_bounds__(256)
 k_matvec_long(MatSet ms, const uint32_t* __restrict__ rows, const Fr28* __restrict__ z, Fr28* __restrict__ out_base, uint32_t n, uint32_t n_vars) {
   __shared__ Fr28 part[256];
@@ -83,16 +88,23 @@ k_matvec_long(MatSet ms, const uint32_t* __restrict__ rows, const Fr28* __restri
   Fr28 acc = Fr28::zero();
   const uint32_t b = ms.rowptr[m][i], e = ms.rowptr[m][i + 1];
   for (uint32_t k = b + threadIdx.x; k < e; k += 256) acc = acc + ld28(val + k) * ld28(z + col[k]);
+  if constexpr (NORM != 0)  // a row of any length the CSR can hold: a lane's share first, then the sum of the 256 shares
+    if ((NORM >> m) & 1) acc = acc * Fr28::one();
   part[threadIdx.x] = acc;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
     if ((int)threadIdx.x < o) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) st28(out_base + (size_t)m * gridDim.y * n + (size_t)blockIdx.y * n + i, part[0]);
+  if (threadIdx.x == 0) {
+    Fr28 v = part[0];
+    if constexpr (NORM != 0)
+      if ((NORM >> m) & 1) v = v * Fr28::one();
+    st28(out_base + (size_t)m * gridDim.y * n + (size_t)blockIdx.y * n + i, v);
+  }
 }
 
-template <int S>
+template <int S, int NORM>
 __global__ void __launch_bounds__(256)
 k_matvec(MatSet ms, const Fr28* __restrict__ z, Fr28* __restrict__ out_base, uint32_t nc, uint32_t n, uint32_t n_pub,
          uint32_t n_vars) {
@@ -126,6 +138,8 @@ k_matvec(MatSet ms, const Fr28* __restrict__ z, Fr28* __restrict__ out_base, uin
     }
     if (lane != 0) return;
   }
+  if constexpr (NORM != 0)
+    if ((NORM >> m) & 1) acc = acc * Fr28::one();
   st28(out + i, acc);
 }
 
@@ -186,6 +200,24 @@ k_quotient(Fr28* __restrict__ a, const Fr28* __restrict__ b, Fr28* __restrict__ 
   st28(a + i, ld28(a + i) * ld28(b + i));
   st28(c + i, ld28(c + i) * n_field);
 }
+
+#ifdef ZKMI_TESTING  // test scaffolding: libzkmi_exp.so only (witness_selftest.hpp)
+// out[0] = max(out[0], |top limb| over v[0 .. n)): how far a vector of the witness map is from the ends of the representation
+__global__ void __launch_bounds__(256)
+k_max_top_limb(const Fr28* __restrict__ v, uint32_t n, uint32_t* __restrict__ out) {
+  uint32_t m = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int32_t t = v[i].l[Fr28::NL - 1];
+    const uint32_t a = t < 0 ? 0u - (uint32_t)t : (uint32_t)t;
+    m = a > m ? a : m;
+  }
+  for (int o = 32; o; o >>= 1) {
+    const uint32_t t = __shfl_down(m, o, 64);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63u) == 0 && m) atomicMax(out, m);
+}
+#endif  // ZKMI_TESTING
 
 // the device-resident assignments of a group, gathered back to back: ONE launch of one-wave workgroups instead of one
 // blit kernel per proof (1 300 __amd_rocclr_copyBuffer launches of 512 threads took 9.6 % of a 2^14 run's kernel time:
@@ -298,6 +330,7 @@ struct zkmi_pk {
   uint32_t* d_rowptr[3] = {nullptr, nullptr, nullptr};
   uint32_t* d_long_rows = nullptr;  // (matrix, row) of every row with more than MATVEC_LONG_ROW terms (k_matvec_long)
   uint32_t n_long_rows = 0;
+  uint32_t norm_mask = 0;  // bit m: the mat-vec of matrix m normalises its row sums (witness_bound.hpp)
   uint32_t* d_col[3] = {nullptr, nullptr, nullptr};
   Fr28* d_val[3] = {nullptr, nullptr, nullptr};
   G1Affine *a_query = nullptr, *b_g1_query = nullptr, *h_query = nullptr, *l_query = nullptr;  // l padded to n_vars
@@ -376,6 +409,8 @@ static hipError_t pk_alloc(zkmi_pk* pk, zkmi_ctx* ctx, const zkmi_r1cs* r) {
           longs.push_back(i);
         }
     pk->n_long_rows = (uint32_t)(longs.size() / 2);
+    const uint32_t* rps[3] = {r->m[0].rowptr.data(), r->m[1].rowptr.data(), r->m[2].rowptr.data()};
+    pk->norm_mask = witness_bound(r->log_n, r->n_pub, r->n_constraints, rps).normalise;
     if (pk->n_long_rows) {
       if ((e = hipMalloc(&pk->d_long_rows, sizeof(uint32_t) * longs.size())) != hipSuccess) return e;
       if ((e = hipMemcpy(pk->d_long_rows, longs.data(), sizeof(uint32_t) * longs.size(), hipMemcpyHostToDevice)) != hipSuccess) return e;
@@ -791,6 +826,30 @@ int32_t zkmi::pk_load_encoded(zkmi_ctx* ctx, const zkmi_r1cs* r, const uint8_t a
   return ZKMI_OK;
 }
 
+// The mat-vec of one group as the witness map queues it: eight lanes per row for one small proof, one lane otherwise, and the
+// listed long rows behind either; the key's normalisation mask selects the instantiation (0 for every key whose sums fit).
+template <int NORM>
+static void launch_matvec_t(const zkmi_pk* pk, const MatSet& ms, bool lanes8, uint32_t G, hipStream_t st) {
+  const uint32_t N = 1u << pk->log_n, nv = pk->n_vars;
+  if (lanes8)
+    hipLaunchKernelGGL((k_matvec<8, NORM>), dim3((8 * N + 63) / 64, 1, 3), dim3(64), 0, st, ms, pk->d_zm, pk->d_a, pk->nc, N, pk->n_pub, nv);
+  else
+    hipLaunchKernelGGL((k_matvec<1, NORM>), dim3((N + 63) / 64, G, 3), dim3(64), 0, st, ms, pk->d_zm, pk->d_a, pk->nc, N, pk->n_pub, nv);
+  if (pk->n_long_rows) hipLaunchKernelGGL(k_matvec_long<NORM>, dim3(pk->n_long_rows, G), dim3(256), 0, st, ms, pk->d_long_rows, pk->d_zm, pk->d_a, N, nv);
+}
+static void launch_matvec(const zkmi_pk* pk, const MatSet& ms, bool lanes8, uint32_t G, hipStream_t st) {
+  switch (pk->norm_mask & 7u) {
+    case 0: return launch_matvec_t<0>(pk, ms, lanes8, G, st);
+    case 1: return launch_matvec_t<1>(pk, ms, lanes8, G, st);
+    case 2: return launch_matvec_t<2>(pk, ms, lanes8, G, st);
+    case 3: return launch_matvec_t<3>(pk, ms, lanes8, G, st);
+    case 4: return launch_matvec_t<4>(pk, ms, lanes8, G, st);
+    case 5: return launch_matvec_t<5>(pk, ms, lanes8, G, st);
+    case 6: return launch_matvec_t<6>(pk, ms, lanes8, G, st);
+    default: return launch_matvec_t<7>(pk, ms, lanes8, G, st);
+  }
+}
+
 extern "C" {
 
 int32_t zkmi_pk_check(zkmi_ctx* ctx, const zkmi_pk* pk, int32_t checks, uint64_t out_where[2]) {
@@ -930,11 +989,7 @@ static int32_t witness_map_dev(zkmi_ctx* ctx, const zkmi_pk* pk, const void* con
     ms.col[m] = pk->d_col[m];
     ms.val[m] = pk->d_val[m];
   }
-  if (G == 1 && pk->log_n <= 16)
-    hipLaunchKernelGGL(k_matvec<8>, dim3((8 * N + 63) / 64, 1, 3), dim3(64), 0, st, ms, pk->d_zm, pk->d_a, pk->nc, N, pk->n_pub, nv);
-  else
-    hipLaunchKernelGGL(k_matvec<1>, dim3((N + 63) / 64, G, 3), dim3(64), 0, st, ms, pk->d_zm, pk->d_a, pk->nc, N, pk->n_pub, nv);
-  if (pk->n_long_rows) hipLaunchKernelGGL(k_matvec_long, dim3(pk->n_long_rows, G), dim3(256), 0, st, ms, pk->d_long_rows, pk->d_zm, pk->d_a, N, nv);
+  launch_matvec(pk, ms, G == 1 && pk->log_n <= 16, G, st);
   Fr28* const d_b = pk->d_a + (size_t)N * G;  // the layout follows the size of THIS group, not the key's maximum
   Fr28* const d_c = pk->d_a + 2 * (size_t)N * G;
   hipLaunchKernelGGL(k_check_sat, dim3((pk->nc + 64) / 64, G), dim3(64), 0, st, pk->d_a, d_b, d_c, pk->d_zm, pk->nc,
@@ -1560,6 +1615,10 @@ int32_t zkmi_selftest_assembly(uint64_t seed, uint32_t iters, uint32_t* out_mism
   *out_mismatches = bad;
   return ZKMI_OK;
 }
+#endif  // ZKMI_TESTING
+
+#ifdef ZKMI_TESTING  // test scaffolding: libzkmi_exp.so only (include/zkmi_testing.h)
+#include "witness_selftest.hpp"
 #endif  // ZKMI_TESTING
 
 int32_t zkmi_groth16_prove(zkmi_ctx* ctx, const zkmi_pk* pk, const uint8_t* z, const uint8_t r_bytes[32],

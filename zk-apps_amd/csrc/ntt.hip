@@ -15,7 +15,11 @@
 //        32-bit top limb (2^252 units): |v| < 2^31 2^252 = 2^28.1 r (BLS12-381) or 2^29.4 r (BN254).  With inputs in
 //        [0, r] -- from_canonical() and every product give that -- N = 2^26 leaves two (BN254: three) further
 //        doublings: oracle/field28_ubsan.cpp measures it, tests/test_gpu_field28.py runs the constant and the
-//        alternating vector at 2^26.  An input that is itself a sum of k such values has log2 k bits less.
+//        alternating vector at 2^26.  The prover's inputs are NOT of that class: the mat-vec hands this transform unreduced
+//        row sums, |v| < 3/2 k r for a row of k terms, and what has to fit is the sum of those over one coherent set (a
+//        stride class of the first pass under a twist, the whole vector without).  The KEY guarantees that: pk_alloc
+//        bounds it from the row lengths (witness_bound.hpp) and has the mat-vec normalise a matrix that would not fit
+//        (tests/witness28.py is the model, tests/test_gpu_witness_bounds.py runs the raw limbs at capacity).
 //
 // Kernel plan (LDS-staged butterflies).  A pass owns up to 10 consecutive
 // butterfly stages: every workgroup stages a tile of 2^S x 2^Q elements in LDS

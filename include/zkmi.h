@@ -579,9 +579,10 @@ int32_t zkmi_pk_check(zkmi_ctx* ctx, const zkmi_pk* pk, int32_t checks, uint64_t
 /* ---- phase-1 transcripts ("powers of tau" with alpha and beta) and transforms of point arrays ------------------- *
  * The first layers of a setup that never sees the toxic waste: a ceremony transcript -- the five point arrays
  * [tau^i]G1, [tau^i]G2, [alpha tau^i]G1, [beta tau^i]G1, [beta]G2 -- resident and checked on the device, and the
- * transform that turns powers of tau into the Lagrange basis [L_i(tau)]G "in the exponent".  Deriving a relation's
- * key from them (the sums over the R1CS columns, the delta contribution) is not in the library yet:
- * zkmi_groth16_setup, with explicit toxic waste, stays the only setup. */
+ * transform that turns powers of tau into the Lagrange basis [L_i(tau)]G "in the exponent"; then the circuit-specific
+ * step: zkmi_groth16_setup_from_srs derives a relation's key from the transcript (the sums over the R1CS columns and the
+ * h query, on the device) and zkmi_pk_contribute applies a phase-2 contribution to delta.  Verifying somebody else's
+ * contribution (the ratio checks by pairing) and the same-ratio checks of the transcript itself are the caller's. */
 /* In-place transform of 2^log_n points in HBM, affine WIRE form (all zero = infinity), natural order in and out:
  * out[i] = sum_k w^(ik) in[k] (forward), out[i] = N^-1 sum_k w^(-ik) in[k] (inverse), w = the root zkmi_ntt_fr uses.
  * The points must be in the r-order subgroup (caller's duty, as for zkmi_pairing_product_dev); a coordinate >= p is
@@ -609,6 +610,19 @@ int32_t zkmi_srs_shape(const zkmi_srs* s, uint64_t out[3]);          /* n_tau_g1
 /* count points of a section (numbered as in out_where above) from `first`, affine WIRE form (96 / 192 B each) */
 int32_t zkmi_srs_read(zkmi_ctx* ctx, const zkmi_srs* s, int32_t section, uint64_t first, uint64_t count, uint8_t* out_wire);
 int32_t zkmi_srs_free(zkmi_srs* s);
+/* A relation's Groth16 key from a phase-1 transcript, gamma = delta = 1 (the state before any phase-2 contribution).
+ * Needs n_tau_g1 >= 2N - 1, n_tau_g2 >= N, n_ab >= N for N = 2^r1cs->log_n; a longer transcript gives the same key.
+ * vk_out as zkmi_groth16_setup.  The transcript is not modified and may be freed afterwards.
+ * ZKMI_ERR_BAD_ARG: a NULL argument, a short transcript, a short vk_cap, a transcript of another context or device;
+ * *out_pk is NULL after every refusal.  The key equals that of zkmi_groth16_setup with the same tau, alpha, beta and gamma = delta = 1, byte for byte. */
+int32_t zkmi_groth16_setup_from_srs(zkmi_ctx* ctx, const zkmi_r1cs* r1cs, const zkmi_srs* srs, zkmi_pk** out_pk,
+                                    uint8_t* vk_out, uint64_t vk_cap);
+/* One phase-2 contribution d (32 B canonical, 0 < d < r), in place on an idle resident key: delta <- d * delta in G1
+ * and G2, h_query and the non-public l_query <- d^-1 * (.).  out_delta_g1 / out_delta_g2 receive the new elements
+ * (the caller patches vk bytes 480..671 with out_delta_g2).  d >= r: ZKMI_ERR_NON_CANONICAL; d = 0 or a NULL argument:
+ * ZKMI_ERR_BAD_ARG; a refused call leaves the key untouched.  Waits for everything queued on the context first. */
+int32_t zkmi_pk_contribute(zkmi_ctx* ctx, zkmi_pk* pk, const uint8_t d[32], uint8_t out_delta_g1[96],
+                           uint8_t out_delta_g2[192]);
 
 /* ---- row a12: the reference's prove/verify surface ------------------------ */
 #define ZKMI_MERKLE_TREE_DEPTH 10 /* shielder/mocked_zk/src/lib.rs:16 */

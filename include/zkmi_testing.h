@@ -159,6 +159,23 @@ int32_t zkmi_selftest_witness_map_stages(zkmi_ctx* ctx, const zkmi_pk* pk, const
  * bases run the shared-bucket schedule, others the windowed one).  Scalars in HBM. */
 int32_t zkmi_selftest_msm_g1_sum2_dev(zkmi_ctx* ctx, const void* d_scalars_a, const void* d_scalars_b, uint64_t n,
                                       const zkmi_bases_g1* bases, uint8_t out_affine[96]);
+/* The column sums of zkmi_groth16_setup_from_srs without a device: csrc/colsum_plan.hpp, csrc/setup_srs.hip.
+ * which numbers the query as zkmi_pk_export_query does: 0 a, 1 b_g1, 2 b_g2, 4 l (all n_vars slots; the first n_pub of l
+ * are gamma_abc_g1).
+ * colsum_plan: the host plan of one query.  out_counts: [0] FAN, [1] terms, [2] items, [3] levels, [4] empty slots.  The
+ * arrays may be NULL (call once for the counts); a capacity (in records) below the count: ZKMI_ERR_BAD_ARG.
+ *   out_terms  12 words per term: point, base selector (0 [L], 1 [alpha L], 2 [beta L]), negate, bit length, k[8]
+ *   out_items  4 words per item, level after level: level, out (bit 31: a final slot, else a partial of that level), first, count
+ *   out_empty  the variables no row mentions
+ * setup_columns_host: the Lagrange bases from explicit tau|alpha|beta by host scalar multiplications (log_n <= 6), the
+ * plan run by the host loop over the per-item bodies the kernels call, the n_vars points in affine WIRE form. */
+int32_t zkmi_selftest_colsum_plan(const zkmi_r1cs* r1cs, int32_t which, uint64_t out_counts[5], uint32_t* out_terms,
+                                  uint64_t cap_terms, uint32_t* out_items, uint64_t cap_items, uint32_t* out_empty,
+                                  uint64_t cap_empty);
+int32_t zkmi_selftest_setup_columns_host(const zkmi_r1cs* r1cs, const uint8_t toxic3[96], int32_t which, uint8_t* out_wire);
+/* The last zkmi_groth16_setup_from_srs of this library, in ms of host clock (every phase ends in a stream wait):
+ * [0] Lagrange transforms, [1] column sums, [2] h query.  One global, last call wins; the product library records nothing. */
+int32_t zkmi_setup_from_srs_phases(double out_ms[3]);
 
 #ifdef __cplusplus
 }

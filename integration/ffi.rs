@@ -100,6 +100,10 @@ extern "C" {
     pub fn zkmi_srs_shape(s: *const zkmi_srs, out: *mut u64) -> i32;
     pub fn zkmi_srs_read(ctx: *mut zkmi_ctx, s: *const zkmi_srs, section: i32, first: u64, count: u64, out_wire: *mut u8) -> i32;
     pub fn zkmi_srs_free(s: *mut zkmi_srs) -> i32;
+    // a relation's key from a transcript (gamma = delta = 1), and one phase-2 contribution to delta, in place
+    pub fn zkmi_groth16_setup_from_srs(ctx: *mut zkmi_ctx, r1cs: *const zkmi_r1cs, srs: *const zkmi_srs, out_pk: *mut *mut zkmi_pk,
+                                       vk_out: *mut u8, vk_cap: u64) -> i32;
+    pub fn zkmi_pk_contribute(ctx: *mut zkmi_ctx, pk: *mut zkmi_pk, d: *const u8, out_delta_g1: *mut u8, out_delta_g2: *mut u8) -> i32;
     pub fn zkmi_ark_vk_read(buf: *const u8, len: u64, compressed: i32, out_vk: *mut u8, vk_cap: u64, out_n_pub: *mut u32, out_consumed: *mut u64) -> i32;
     pub fn zkmi_pk_shape(pk: *const zkmi_pk, n_vars: *mut u32, n_pub: *mut u32, log_n: *mut u32) -> i32;
     pub fn zkmi_host_info(out: *mut u32) -> i32;

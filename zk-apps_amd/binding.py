@@ -530,6 +530,28 @@ class Zkmi:
         self._chk(self.lib.zkmi_r1cs_create(C.c_uint32(n_vars), C.c_uint32(n_pub), C.c_uint32(nc), *args, C.byref(h)))
         return R1cs(self, h)
 
+    def selftest_colsum_plan(self, r1cs, which):
+        """Testing library: the host plan of one column query of groth16_setup_from_srs (which: 0 a, 1 b_g1, 2 b_g2, 4 l) ->
+        dict(fan, terms [(point, base, neg, bits, k)], items [(level, out, first, count)], empty [slot])."""
+        cnt = (C.c_uint64 * 5)()
+        fn = self.tlib.zkmi_selftest_colsum_plan
+        self._chk(fn(r1cs.h, C.c_int32(which), cnt, None, C.c_uint64(0), None, C.c_uint64(0), None, C.c_uint64(0)))
+        nt, ni, ne = int(cnt[1]), int(cnt[2]), int(cnt[4])
+        t, i, e = (C.c_uint32 * max(1, 12 * nt))(), (C.c_uint32 * max(1, 4 * ni))(), (C.c_uint32 * max(1, ne))()
+        self._chk(fn(r1cs.h, C.c_int32(which), cnt, t, C.c_uint64(nt), i, C.c_uint64(ni), e, C.c_uint64(ne)))
+        terms = [(t[12 * q], t[12 * q + 1], t[12 * q + 2], t[12 * q + 3], sum(t[12 * q + 4 + w] << (32 * w) for w in range(8)))
+                 for q in range(nt)]
+        items = [tuple(i[4 * q : 4 * q + 4]) for q in range(ni)]
+        return {"fan": int(cnt[0]), "levels": int(cnt[3]), "terms": terms, "items": items, "empty": list(e[:ne])}
+
+    def selftest_setup_columns_host(self, r1cs, toxic3, which, n_vars):
+        """Testing library: one column query of the key from explicit tau|alpha|beta, the plan run by the host loop -> wire bytes."""
+        assert len(toxic3) == 96
+        w = 192 if which == 2 else 96
+        out = (C.c_uint8 * (w * n_vars))()
+        self._chk(self.tlib.zkmi_selftest_setup_columns_host(r1cs.h, _buf(toxic3), C.c_int32(which), out))
+        return bytes(out)
+
     # ---- reference prove/verify surface (mocked_zk mirror) -------------------
     def account_new(self, tokens):
         arr = (Scalar * TOKENS_NUMBER)(*[scalar(t) for t in tokens])
@@ -1028,6 +1050,23 @@ class Context:
         self._chk(self.lib.zkmi_srs_generate(self.h, _buf(toxic), C.c_uint32(log_n), C.byref(h)))
         return Srs(self, h)
 
+    def groth16_setup_from_srs(self, r1cs, srs, vk_cap=None):
+        """zkmi_groth16_setup_from_srs: the relation's key from a phase-1 transcript, gamma = delta = 1 -> (ProvingKey, vk)."""
+        cap = 672 + 96 * r1cs.n_pub if vk_cap is None else vk_cap
+        vk = (C.c_uint8 * max(1, cap))()
+        h = C.c_void_p()
+        rc = self.lib.zkmi_groth16_setup_from_srs(self.h, r1cs.h, srs.h, C.byref(h), vk, C.c_uint64(cap))
+        if rc != 0:
+            assert not h.value
+        self._chk(rc)
+        return ProvingKey(self, h, r1cs), bytes(vk)
+
+    def setup_from_srs_phases(self):
+        """Testing library: ms of the last groth16_setup_from_srs made through it (transforms, column sums, h query)."""
+        out = (C.c_double * 3)()
+        self._chk(self.z.tlib.zkmi_setup_from_srs_phases(out))
+        return tuple(out)
+
     def pk_load(self, r1cs, alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2, a_q, b1_q, b2_q, h_q, l_q):
         h = C.c_void_p()
         self._chk(
@@ -1211,6 +1250,20 @@ class ProvingKey:
             return int(where[0]), int(where[1])
         self.ctx._chk(rc)
         return None
+
+    def contribute(self, d):
+        """zkmi_pk_contribute: one phase-2 contribution d (32 B canonical, 0 < d < r) in place -> (delta_g1, delta_g2), the
+        new elements; the caller patches vk[480:672] with delta_g2."""
+        assert len(d) == 32
+        d1, d2 = (C.c_uint8 * 96)(), (C.c_uint8 * 192)()
+        self.ctx._chk(self.ctx.lib.zkmi_pk_contribute(self.ctx.h, self.h, _buf(d), d1, d2))
+        return bytes(d1), bytes(d2)
+
+    def export_g1_elems(self):
+        """zkmi_pk_export_g1_elems: (beta_g1, delta_g1)."""
+        b, d = (C.c_uint8 * 96)(), (C.c_uint8 * 96)()
+        self.ctx._chk(self.ctx.lib.zkmi_pk_export_g1_elems(self.h, b, d))
+        return bytes(b), bytes(d)
 
     def schedule_state(self):
         """zkmi_pk_schedule_state: (B1 folded into the L + H reduction?, non-zero digits of the last finished proof's

@@ -35,6 +35,7 @@
 #include "r1cs.hpp"
 #include "points.hpp"
 #include "points_ntt.hpp"
+#include "setup_srs.hpp"
 #include "witness_bound.hpp"
 
 namespace zkmi {
@@ -550,6 +551,57 @@ static hipError_t pk_convert_queries(zkmi_pk* pk) {
   return hipSuccess;
 }
 
+// h and l changed (zkmi_pk_contribute): their device MSM copies and digit tables again, as pk_convert_queries made them
+static hipError_t pk_convert_h_l(zkmi_pk* pk) {
+  hipStream_t st = pk->ctx->stream;
+  const uint64_t N = 1ull << pk->log_n;
+  hipError_t e;
+  if ((e = bases_convert<Fq28>(pk->l_query, pk->l28, pk->n_vars, st)) != hipSuccess) return e;
+  if ((e = bases_convert<Fq28>(pk->h_query, pk->h28, N, st)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_bitrev_points<Affine<Fq28>>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, pk->h28,
+                     pk->h28_rev, (int)pk->log_n);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (pk->shared) {
+    Affine<Fq28>*l_tab = nullptr, *h_tab = nullptr;
+    e = msm_build_table<Fq28>(pk->l28 + 1, pk->n_vars - 1, msm_make_plan_shared(pk->n_vars - 1), &l_tab, st);
+    if (e == hipSuccess) e = msm_build_table<Fq28>(pk->h28_rev, N, msm_make_plan_shared(N), &h_tab, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+      if (l_tab) (void)hipFree(l_tab);
+      if (h_tab) (void)hipFree(h_tab);
+      return e;
+    }
+    if (pk->l_tab) (void)hipFree(pk->l_tab);
+    if (pk->h_tab) (void)hipFree(pk->h_tab);
+    pk->l_tab = l_tab, pk->h_tab = h_tab;
+  }
+  return hipStreamSynchronize(st);
+}
+
+// The tail every setup shares.  The five queries are on the device, the public part of l still in place: it goes to
+// `ic` (the verifying key's gamma_abc_g1) and is blanked in the key; the constant summands and the device MSM copies follow.
+static hipError_t pk_finish_queries(zkmi_pk* pk, std::vector<G1Affine>* ic) {
+  const uint32_t np = pk->n_pub;
+  ic->resize(np);
+  hipError_t e = hipMemcpy(ic->data(), pk->l_query, sizeof(G1Affine) * np, hipMemcpyDeviceToHost);
+  // the public part of the L query belongs to the verifying key; blank it in the proving key
+  if (e == hipSuccess) e = hipMemset(pk->l_query, 0, sizeof(G1Affine) * np);
+  if (e == hipSuccess) e = hipMemcpy(&pk->a0, pk->a_query, sizeof(G1Affine), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&pk->b1_0, pk->b_g1_query, sizeof(G1Affine), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&pk->b2_0, pk->b_g2_query, sizeof(G2Affine), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = pk_convert_queries(pk);
+  return e;
+}
+// alpha, beta and delta are set: the tables of proof assembly and the verifying key's bytes
+static void pk_finish_elements(zkmi_pk* pk, const G2Affine& gamma_g2, const std::vector<G1Affine>& ic, uint8_t* vk_out) {
+  pk_build_delta_tables(pk);
+  g1_to_wire(pk->alpha_g1, vk_out);
+  g2_to_wire(pk->beta_g2, vk_out + 96);
+  g2_to_wire(gamma_g2, vk_out + 288);
+  g2_to_wire(pk->delta_g2, vk_out + 480);
+  for (size_t j = 0; j < ic.size(); j++) g1_to_wire(ic[j], vk_out + 672 + 96ull * j);
+}
+
 static Fr fr_from_u64(uint64_t v) {
   Fr a = Fr::zero();
   a.l[0] = (uint32_t)v;
@@ -563,6 +615,42 @@ static void fr_limbs(const Fr& mont, uint32_t k[8]) {
 }
 
 namespace zkmi {
+// Lagrange basis at tau:  L_i = (tau^N - 1)/N * w^i / (tau - w^i)
+bool lagrange_basis_at(uint32_t log_n, const Fr& tau, std::vector<Fr>* out_L, Fr* out_zt) {
+  const uint32_t N = 1u << log_n;
+  Fr tn = tau;
+  for (uint32_t i = 0; i < log_n; i++) tn = tn.sqr();
+  const Fr zt = tn - Fr::one();
+  if (zt.is_zero()) return false;
+  const Fr w = fr_root_of_unity((int)log_n);
+  std::vector<Fr> L(N), den(N);
+  {
+    Fr wi = Fr::one();
+    for (uint32_t i = 0; i < N; i++) {
+      den[i] = tau - wi;
+      L[i] = wi;
+      wi = wi * w;
+    }
+    // batch inversion
+    std::vector<Fr> pre(N);
+    Fr run = Fr::one();
+    for (uint32_t i = 0; i < N; i++) {
+      pre[i] = run;
+      run = run * den[i];
+    }
+    Fr inv = run.inv();
+    const Fr scale = zt * fr_from_u64(N).inv();
+    for (uint32_t i = N; i-- > 0;) {
+      Fr di = inv * pre[i];
+      inv = inv * den[i];
+      L[i] = L[i] * di * scale;
+    }
+  }
+  out_L->swap(L);
+  *out_zt = zt;
+  return true;
+}
+
 template <class F>
 hipError_t fixed_base_table(const Affine<F>& base, Affine<F>** d_table) {
   std::vector<Affine<F>> t(32 * 256);
@@ -618,35 +706,9 @@ int32_t zkmi_groth16_setup(zkmi_ctx* ctx, const zkmi_r1cs* r, const uint8_t toxi
     if (!fr_from_wire(toxic + 32 * i, tw[i])) return ctx->fail(ZKMI_ERR_NON_CANONICAL, "toxic waste >= r");
   if (gamma.is_zero() || delta.is_zero()) return ctx->fail(ZKMI_ERR_BAD_ARG, "gamma/delta must be non-zero");
   const uint32_t N = 1u << r->log_n, nv = r->n_vars, np = r->n_pub, nc = r->n_constraints;
-  // Lagrange basis at tau:  L_i = (tau^N - 1)/N * w^i / (tau - w^i)
-  Fr tn = tau;
-  for (uint32_t i = 0; i < r->log_n; i++) tn = tn.sqr();
-  const Fr zt = tn - Fr::one();
-  if (zt.is_zero()) return ctx->fail(ZKMI_ERR_BAD_ARG, "tau is in the evaluation domain");
-  const Fr w = fr_root_of_unity((int)r->log_n);
-  std::vector<Fr> L(N), den(N);
-  {
-    Fr wi = Fr::one();
-    for (uint32_t i = 0; i < N; i++) {
-      den[i] = tau - wi;
-      L[i] = wi;
-      wi = wi * w;
-    }
-    // batch inversion
-    std::vector<Fr> pre(N);
-    Fr run = Fr::one();
-    for (uint32_t i = 0; i < N; i++) {
-      pre[i] = run;
-      run = run * den[i];
-    }
-    Fr inv = run.inv();
-    const Fr scale = zt * fr_from_u64(N).inv();
-    for (uint32_t i = N; i-- > 0;) {
-      Fr di = inv * pre[i];
-      inv = inv * den[i];
-      L[i] = L[i] * di * scale;
-    }
-  }
+  Fr zt;
+  std::vector<Fr> L;
+  if (!lagrange_basis_at(r->log_n, tau, &L, &zt)) return ctx->fail(ZKMI_ERR_BAD_ARG, "tau is in the evaluation domain");
   std::vector<Fr> a(nv, Fr::zero()), b(nv, Fr::zero()), c(nv, Fr::zero());
   for (uint32_t j = 0; j < np; j++) a[j] = L[nc + j];
   std::vector<Fr>* dst[3] = {&a, &b, &c};
@@ -681,14 +743,8 @@ int32_t zkmi_groth16_setup(zkmi_ctx* ctx, const zkmi_r1cs* r, const uint8_t toxi
   if (e == hipSuccess) e = fixed_base_batch<Fq2>(ctx, t2, b, pk->b_g2_query);
   if (e == hipSuccess) e = fixed_base_batch<Fq>(ctx, t1, lq, pk->l_query);
   if (e == hipSuccess) e = fixed_base_batch<Fq>(ctx, t1, hq, pk->h_query);
-  std::vector<G1Affine> ic(np);
-  if (e == hipSuccess) e = hipMemcpy(ic.data(), pk->l_query, sizeof(G1Affine) * np, hipMemcpyDeviceToHost);
-  // the public part of the L query belongs to the verifying key; blank it in the proving key
-  if (e == hipSuccess) e = hipMemset(pk->l_query, 0, sizeof(G1Affine) * np);
-  if (e == hipSuccess) e = hipMemcpy(&pk->a0, pk->a_query, sizeof(G1Affine), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(&pk->b1_0, pk->b_g1_query, sizeof(G1Affine), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(&pk->b2_0, pk->b_g2_query, sizeof(G2Affine), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = pk_convert_queries(pk);
+  std::vector<G1Affine> ic;
+  if (e == hipSuccess) e = pk_finish_queries(pk, &ic);
   if (t1) (void)hipFree(t1);
   if (t2) (void)hipFree(t2);
   if (e != hipSuccess) {
@@ -709,13 +765,70 @@ int32_t zkmi_groth16_setup(zkmi_ctx* ctx, const zkmi_r1cs* r, const uint8_t toxi
   pk->delta_g1 = mul1(delta);
   pk->beta_g2 = mul2(beta);
   pk->delta_g2 = mul2(delta);
-  pk_build_delta_tables(pk);
-  g1_to_wire(pk->alpha_g1, vk_out);
-  g2_to_wire(pk->beta_g2, vk_out + 96);
-  g2_to_wire(mul2(gamma), vk_out + 288);
-  g2_to_wire(pk->delta_g2, vk_out + 480);
-  for (uint32_t j = 0; j < np; j++) g1_to_wire(ic[j], vk_out + 672 + 96ull * j);
+  pk_finish_elements(pk, mul2(gamma), ic, vk_out);
   *out_pk = pk;
+  return ZKMI_OK;
+}
+
+int32_t zkmi_groth16_setup_from_srs(zkmi_ctx* ctx, const zkmi_r1cs* r, const zkmi_srs* srs, zkmi_pk** out_pk, uint8_t* vk_out,
+                                    uint64_t vk_cap) {
+  if (out_pk) *out_pk = nullptr;
+  ZK_ENTER(ctx);
+  if (!r || !srs || !out_pk || !vk_out) return ZKMI_ERR_BAD_ARG;
+  if (srs->ctx != ctx || srs->device != ctx->device) return ctx->fail(ZKMI_ERR_BAD_ARG, "transcript of another context");
+  if (vk_cap < 672 + 96ull * r->n_pub) return ctx->fail(ZKMI_ERR_BAD_ARG, "vk buffer too small");
+  const uint64_t N = 1ull << r->log_n;
+  if (r->log_n > 26 || (uint64_t)r->n_constraints + r->n_pub > N) return ctx->fail(ZKMI_ERR_BAD_ARG, "constraints + instance exceed the domain");
+  if (srs->n_tau_g1 < 2 * N - 1 || srs->n_tau_g2 < N || srs->n_ab < N)
+    return ctx->fail(ZKMI_ERR_BAD_ARG, "transcript too short: needs 2N - 1 powers in G1, N in G2, N of alpha and beta");
+  zkmi_pk* pk = new (std::nothrow) zkmi_pk();
+  if (!pk) return ZKMI_ERR_BAD_ARG;
+  hipError_t e = pk_alloc(pk, ctx, r);
+  if (e != hipSuccess) {
+    delete pk;
+    return ctx->hip_fail(e, "pk alloc");
+  }
+  const int32_t rc = setup_queries_from_srs(ctx, r, srs, {pk->a_query, pk->b_g1_query, pk->l_query, pk->h_query, pk->b_g2_query},
+                                            &pk->alpha_g1, &pk->beta_g1);
+  if (rc != ZKMI_OK) {
+    delete pk;
+    return rc;
+  }
+  std::vector<G1Affine> ic;
+  if ((e = pk_finish_queries(pk, &ic)) != hipSuccess) {
+    delete pk;
+    return ctx->hip_fail(e, "groth16 setup from transcript");
+  }
+  // gamma = delta = 1: the state before any phase-2 contribution
+  pk->delta_g1 = g1_generator();
+  pk->beta_g2 = srs->beta_g2;
+  pk->delta_g2 = g2_generator();
+  pk_finish_elements(pk, g2_generator(), ic, vk_out);
+  *out_pk = pk;
+  return ZKMI_OK;
+}
+
+int32_t zkmi_pk_contribute(zkmi_ctx* ctx, zkmi_pk* pk, const uint8_t d[32], uint8_t out_delta_g1[96], uint8_t out_delta_g2[192]) {
+  ZK_ENTER(ctx);
+  if (!pk || !d || !out_delta_g1 || !out_delta_g2) return ZKMI_ERR_BAD_ARG;
+  if (pk->ctx != ctx || pk->device != ctx->device) return ctx->fail(ZKMI_ERR_BAD_ARG, "key of another context");
+  Fr dm;
+  if (!fr_from_wire(d, &dm)) return ctx->fail(ZKMI_ERR_NON_CANONICAL, "contribution >= r");
+  if (dm.is_zero()) return ctx->fail(ZKMI_ERR_BAD_ARG, "contribution must be non-zero");
+  ZK_HIP(ctx, ctx->drain());  // the key is idle: nothing queued earlier still reads its tables
+  const uint64_t N = 1ull << pk->log_n;
+  uint32_t k[8];
+  fr_limbs(dm.inv(), k);
+  int32_t rc = points_scale_resident<Fq>(ctx, pk->h_query, N - 1, k);
+  if (rc == ZKMI_OK) rc = points_scale_resident<Fq>(ctx, pk->l_query + pk->n_pub, pk->n_vars - pk->n_pub, k);
+  if (rc != ZKMI_OK) return rc;
+  ZK_HIP(ctx, pk_convert_h_l(pk));
+  fr_limbs(dm, k);
+  pk->delta_g1 = scalar_mul(G1XYZZ::from_affine(pk->delta_g1), k, 8).to_affine();
+  pk->delta_g2 = scalar_mul(G2XYZZ::from_affine(pk->delta_g2), k, 8).to_affine();
+  pk_build_delta_tables(pk);
+  g1_to_wire(pk->delta_g1, out_delta_g1);
+  g2_to_wire(pk->delta_g2, out_delta_g2);
   return ZKMI_OK;
 }
 

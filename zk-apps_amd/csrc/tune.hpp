@@ -26,6 +26,10 @@ inline int tune_env(const char* name, int dflt) {
 #else
 #define ZK_TUNE(name, dflt) (dflt)
 #endif
+// Column sums of a key derivation from a transcript (colsum_plan.hpp, setup_srs.hip): inputs per work item.  A constant of
+// both libraries, not a switch: the plan, the kernels' range checks and the tests read it.  8 keeps a column of 2^13 terms
+// at five launches and a lane's chain of additions short; DESIGN.md 5.7 says what was and what was not measured.
+constexpr unsigned COLSUM_FAN = 8;
 // ZKMI_DEBUG (both libraries): 1 = diagnostics of failing launches on stderr, 2 = also host-side timestamps of single proofs
 inline int debug_level() {
   static const int v = [] {

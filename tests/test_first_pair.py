@@ -197,6 +197,48 @@ def test_first_pair_cases_match_the_cpp_oracle(zk, ctx, group, n):
     check_group(zk, ctx, group, n)
 
 
+# k_accum_heavy_nc deals a heavy bucket out in wave-items of 64 lanes (G2: 32 lane pairs) x PL consecutive entries, lane l
+# adding entries l, l + 64, ... of its item; PL is MSM_HNC_MIN_PL = 8 while the partial sums fit the pool.  n = 5 (G2: 10) full
+# items + a last one of 1, 63, 64, 65 (G2: 1, 31, 32, 33) entries: the lanes whose entry count differs by one sit in that item.
+HNC_MIN_PL, HNC_POOL, HNC_ENT = 8, 131072, 1024  # msm_impl.hpp MSM_HNC_MIN_PL, MSM_HNC_POOL, MSM_HNC_ENT
+HEAVY_TAILS = [(1, 5 * 64 * HNC_MIN_PL + t) for t in (1, 63, 64, 65)] + [(2, 10 * 32 * HNC_MIN_PL + t) for t in (1, 31, 32, 33)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("group,n", HEAVY_TAILS)
+def test_heavy_bucket_chains_with_every_tail_of_the_last_wave_item(zk, ctx, group, n):
+    """The nine points of test_msm_degenerate_bases_and_scalars (G, G, -G, G, infinity, 2G, -2G, 3G, 3G) repeated and cut
+    to n terms, all with ONE scalar: one heavy bucket of n entries per window.  The lanes of k_accum_heavy_nc[_g2] meet
+    infinity as first and as second entry and P + P and P - P in the pair step, and the last wave-item leaves lanes with one
+    entry fewer than their neighbours, or none.  The plain MSM and the MSM over prepared bases against the C++ oracle's bytes.
+    The tail sizes are those of the PLAIN run (windowed plan, asserted below); over prepared bases the windows share one bucket
+    set, so a heavy bucket there holds n entries per window with the same digit and its last wave-item is another."""
+    from oracle import cpp as ocpp
+
+    assert (group, n) in [(1, 2561), (1, 2623), (1, 2624), (1, 2625), (2, 2561), (2, 2591), (2, 2592), (2, 2593)]
+    c, nd, parts, nb, seg_log, heavy_thr = zk.msm_plan_query(n, False)
+    lanes = 64 if group == 1 else 32
+    # the bucket is heavy, and k_heavy_plan picks the minimum of points per lane: ceil(heavy entries / room) is below it
+    assert n > heavy_thr and max(nd, parts) * n <= HNC_MIN_PL * (HNC_POOL - lanes * HNC_ENT), (c, nd, parts, heavy_thr)
+    F, G = (ec.Fq, ec.G1) if group == 1 else (ec.Fq2, ec.G2)
+    mul = ec.g1_mul if group == 1 else ec.g2_mul
+    to_b = ec.g1_to_bytes if group == 1 else ec.g2_to_bytes
+    width = 96 if group == 1 else 192
+    P2, P3 = mul(2), mul(3)
+    nine = [to_b(p) if p is not None else bytes(width) for p in (G, G, ec.pt_neg(F, G), G, None, P2, ec.pt_neg(F, P2), P3, P3)]
+    bases = b"".join(nine[i % 9] for i in range(n))
+    scalars = ec.fr_to_bytes(0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890AB % R) * n
+    want = (ocpp.msm_g1 if group == 1 else ocpp.msm_g2)(scalars, bases)
+    b = (ctx.bases_g1 if group == 1 else ctx.bases_g2)(bases)
+    msm = ctx.msm_g1 if group == 1 else ctx.msm_g2
+    plain = msm(scalars, b)
+    b.prepare()
+    prepared = msm(scalars, b)
+    b.free()
+    assert plain == want, (group, n, "plain", plain.hex(), want.hex())
+    assert prepared == want, (group, n, "prepared", prepared.hex(), want.hex())
+
+
 _CHILD = r"""
 import sys
 sys.path[:0] = [%r, %r]
@@ -212,12 +254,14 @@ print("first pair ok")
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [{"ZKMI_SOLO_SPLIT_G2": "0"}, {"ZKMI_FORCE_MULTI": "1", "ZKMI_SOLO_SPLIT": "0", "ZKMI_SOLO_SPLIT_G2": "0"}],
-                         ids=["g2_nc", "multi_form"])
+@pytest.mark.parametrize("env", [{"ZKMI_SOLO_SPLIT_G2": "0"}, {"ZKMI_FORCE_MULTI": "1", "ZKMI_SOLO_SPLIT": "0", "ZKMI_SOLO_SPLIT_G2": "0"},
+                                 {"ZKMI_ACCUM_W2": "1"}],
+                         ids=["g2_nc", "multi_form", "two_waves"])
 def test_first_pair_cases_in_the_one_lane_kernels_at_small_sizes(env):
     """Below 2^15 (G2) / 2^16 (G1 multi form) buckets a lone MSM of the product library runs the two-lanes-per-bucket kernels.
     The A/B library's switches send the same small inputs through k_accum_g2_nc and through the multi form of
-    k_accum_g1_nc, the kernels of the prover's pipeline (a child process: the switches are read once per process)."""
+    k_accum_g1_nc, the kernels of the prover's pipeline (a child process: the switches are read once per process); and
+    through k_accum_g1_nc_w2, the same body capped at two waves per SIMD, which nothing but the pipelined big MSM selects."""
     assert os.path.exists(EXP_LIB), "zk-apps_amd/libzkmi_exp.so missing: run __graft_entry__.build() (make experiments)"
     code = _CHILD % (ROOT, os.path.join(ROOT, "tests"), EXP_LIB)
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, **env))

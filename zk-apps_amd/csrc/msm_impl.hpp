@@ -29,8 +29,8 @@
 //                 over 16 consecutive segsum entries -- segsum2 and segt2, see TreeLevel2
 //   6 k_treesum   block/(window, job[, slice]) : plain sums (LDS tree) of segw, and of
 //                 segsum over {t : bit j of t set}; small plans: slices + k_treesum_final
-//   Steps 5 - 6 and the two k_accum_* lines of step 4 have ONE body per algorithm, over a lane layout (OneLane<F>: a lane per
-//   point; LanePair: a G2 point across a lane pair, the _g2_split entry points): see "Lane layouts" below.
+//   Steps 4 - 6 have ONE body per algorithm, over a lane layout (OneLane<F>: a lane per point; LanePair: a G2 point across a
+//   lane pair): see "Lane layouts" and "The two accumulation chains" below.
 //   host: window_w = P[w][0] + SEG * sum_j 2^j P[w][1+j];  result = sum_w 2^(c w) window_w
 //         (with 5b: window_w = P[w][0] + SEG * (T[w] + 16 * sum_j 2^j P2[w][1+j]), windows_from_partials)
 #pragma once
@@ -154,9 +154,279 @@ __device__ __forceinline__ bool affine_is_zero_words(const Affine<Fp28<P>>& p) {
   return o == 0;
 }
 
-// G1 (and BN254 G1): thread per bucket, next table entry prefetched through ONE LDS buffer per wave
-// (the entry is read into registers at the top of the iteration, so the buffer is free for the next
-// direct-to-LDS load straight away): 7 KB per wave.
+// ---------------------------------------------------------------------------------------------
+// Lane layouts.  The accumulation chains and every reduction-side algorithm (redo, heavy buckets, segment sums, tree sums)
+// have ONE body each, written over a layout L that says how a point lies across lanes; the __global__ entry points around a
+// body differ in layout, stride and __launch_bounds__ only.
+//   OneLane<F>  a lane per point (G1, BN254 G1; the unsplit G2 tree sum of the A/B library)
+//   LanePair    a lane pair per G2 point, one Fq2 component per lane (field28.hpp Fq2P, see k_accum_g2_nc): per-lane state
+//               is that of a G1 addition.  The unsplit forms are 330-register kernels with 45-75 us per dependent addition:
+//               0.8 ms for one 600-point bucket of a 2^14 proof, on the critical path of the G2 reduction; and 0.1 ms to
+//               place an EMPTY redo kernel.
+// Memory layouts are the unsplit ones for both.  Thread i (of the workgroup, or of the grid) is lane `comp` = i % LANES of
+// point i / LANES, and every branch around an addition is uniform over the lanes of a point.
+// ---------------------------------------------------------------------------------------------
+template <class F>
+struct OneLane {
+  typedef XYZZ<F> Stored;                             // the point in memory
+  typedef XYZZ<F> P;                                  // what a lane holds of it
+  typedef XYZZ<typename HostFieldOf<F>::type> Host;   // the host-representation point
+  typedef Affine<F> Base;                             // a table entry in memory
+  static constexpr uint32_t LANES = 1;
+  __device__ __forceinline__ static P load(const Stored* p, uint32_t) { return load_vec(p); }
+  __device__ __forceinline__ static void store(Stored* p, const P& v, uint32_t) { store_vec(p, v); }
+  __device__ __forceinline__ static void store_host(Host* p, const P& v, uint32_t) {
+    const Host o = {fq_from_fq28(v.x), fq_from_fq28(v.y), fq_from_fq28(v.zz), fq_from_fq28(v.zzz)};
+    store_vec(p, o);
+  }
+  // the table entry of a sorted[] word, negated where the word's sign bit is set
+  __device__ __forceinline__ static Affine<F> load_affine(const Base* bases, uint32_t v, uint32_t) {
+    Affine<F> p = load_vec(bases + (v & 0x7fffffffu));
+    if (v >> 31) p.y = p.y.neg();
+    return p;
+  }
+  // heavy_marker() left by k_accum_heavy_nc: "infinity" with zzz word 0 set; *empty: all zz words zero, marker or not
+  __device__ __forceinline__ static bool is_marker(const P& v, uint32_t, bool* empty) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < F::NL; i++) o |= (uint32_t)v.zz.l[i];
+    *empty = o == 0;
+    return o == 0 && v.zzz.l[0] == 1;
+  }
+  // a coordinate as the lane at distance `dist` holds it
+  __device__ __forceinline__ static F shfl_xor(const F& a, int dist) {
+    F r;
+#pragma unroll
+    for (int i = 0; i < F::NL; i++) r.l[i] = __shfl_xor(a.l[i], dist);
+    return r;
+  }
+};
+struct LanePair {
+  typedef XYZZ<Fq2_28> Stored;  // x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1: lane `comp` reads / writes every second one
+  typedef XYZZ<Fq2P> P;
+  typedef XYZZ<Fq2> Host;
+  typedef Affine<Fq2_28> Base;
+  static constexpr uint32_t LANES = 2;
+  __device__ __forceinline__ static P load(const Stored* p, uint32_t comp) {
+    const Fq28* s = reinterpret_cast<const Fq28*>(p);
+    P r;
+    r.x.v = ld_comp(s + comp);
+    r.y.v = ld_comp(s + 2 + comp);
+    r.zz.v = ld_comp(s + 4 + comp);
+    r.zzz.v = ld_comp(s + 6 + comp);
+    return r;
+  }
+  __device__ __forceinline__ static void store(Stored* p, const P& v, uint32_t comp) {
+    Fq28* d = reinterpret_cast<Fq28*>(p);
+    st_comp(d + comp, v.x.v);
+    st_comp(d + 2 + comp, v.y.v);
+    st_comp(d + 4 + comp, v.zz.v);
+    st_comp(d + 6 + comp, v.zzz.v);
+  }
+  // what a pair of k_accum_heavy_nc_g2 without a partial sum leaves: infinity, and `marked` -- it met P + P or P - P,
+  // k_accum_heavy_g2_split recomputes the pair's points -- with zzz.c0 word 0 = 1 (ONE store path for both: a branch of
+  // its own for the plain infinity cost the kernel 8 - 52 bytes of scratch)
+  __device__ __forceinline__ static void store_marker(Stored* p, bool marked, uint32_t comp) {
+    P m = P::infinity();
+    m.zzz.v.l[0] = (marked && comp == 0) ? 1 : 0;
+    store(p, m, comp);
+  }
+  __device__ __forceinline__ static void store_host(Host* p, const P& v, uint32_t comp) {
+    Fq* d = reinterpret_cast<Fq*>(p);
+    d[comp] = fq_from_fq28(v.x.v);
+    d[2 + comp] = fq_from_fq28(v.y.v);
+    d[4 + comp] = fq_from_fq28(v.zz.v);
+    d[6 + comp] = fq_from_fq28(v.zzz.v);
+  }
+  // The lane's component of the table entry of a sorted[] word, NO sign applied (the caller does: first point, or folded
+  // into the addition); true = the point at infinity.  Infinity = all four components exact zeros: OR of this lane's words,
+  // combined with the partner's; the lowest limb of y decides for all but 2^-56 of the finite entries, the full test runs
+  // behind that (pair-uniform) branch.  Each DPP swap stands in front of the branch that depends on it.
+  __device__ __forceinline__ static bool load_entry(const Base* bases, uint32_t v, uint32_t comp, Affine<Fq2P>& p) {
+    const Fq28* src = reinterpret_cast<const Fq28*>(bases + (v & 0x7fffffffu));  // x.c0 x.c1 y.c0 y.c1
+    p.x.v = ld_comp(src + comp);
+    p.y.v = ld_comp(src + 2 + comp);
+    uint32_t o = (uint32_t)p.y.v.l[0];
+    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
+    if (o != 0) return false;
+#pragma unroll
+    for (int i = 0; i < Fq28::NL; i++) o |= (uint32_t)p.x.v.l[i] | (uint32_t)p.y.v.l[i];
+    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
+    return o == 0;
+  }
+  __device__ __forceinline__ static Affine<Fq2P> load_affine(const Base* bases, uint32_t v, uint32_t comp) {
+    const Fq28* src = reinterpret_cast<const Fq28*>(bases + (v & 0x7fffffffu));  // x.c0 x.c1 y.c0 y.c1
+    Affine<Fq2P> p;
+    p.x.v = ld_comp(src + comp);
+    p.y.v = ld_comp(src + 2 + comp);
+    if (v >> 31) p.y = p.y.neg();
+    return p;
+  }
+  // the marker of k_accum_heavy_nc_g2 is zzz.c0 word 0: both tests ORed over the pair with one DPP swap each
+  __device__ __forceinline__ static bool is_marker(const P& v, uint32_t comp, bool* empty) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < Fq28::NL; i++) o |= (uint32_t)v.zz.v.l[i];
+    uint32_t mk = (comp == 0 && v.zzz.v.l[0] == 1) ? 1u : 0u;
+    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
+    mk |= (uint32_t)__builtin_amdgcn_mov_dpp((int)mk, 0xB1, 0xF, 0xF, true);
+    *empty = o == 0;
+    return o == 0 && mk == 1;
+  }
+  __device__ __forceinline__ static Fq2P shfl_xor(const Fq2P& a, int dist) { return {OneLane<Fq28>::shfl_xor(a.v, dist)}; }
+};
+
+// ---------------------------------------------------------------------------------------------
+// The two accumulation chains.  accum_first starts a sum with the first finite entry of sorted[j], sorted[j + STRIDE], ...
+// (x and y, the digit's sign applied; j ends up behind that entry; false: there was none), accum_chain adds the finite
+// entries behind it and returns true when an addition met P + P or P - P (the caller hands the bucket to the redo list, or
+// leaves a marker), through ONE exit behind its loops.  FIRST_IS_AFFINE: acc holds x and y of one affine point, and the
+// first finite entry behind it is added with madd_affine_pair (4M + 2S); otherwise all four coordinates are set.  They are
+// two bodies because they are two loop shapes, each the one its kernels' allocation stands on:
+//   OneLane   the next entry prefetched through the wave's LDS column (PrefetchTile), the pair step ONE peeled iteration,
+//             a count-down of `rem` entries (the light kernel's zero-scratch allocation needs the count)
+//   LanePair  entries loaded through registers (LanePair::load_entry), the pair step a search loop, j < end (wave-uniform
+//             in the heavy kernel, where a per-lane count costs 4 - 5 registers)
+// ---------------------------------------------------------------------------------------------
+// The per-wave prefetch column of the one-lane chain: one table entry per lane, fetched by seven (BLS12-381 Fq) or five
+// (BN254 Fq) direct-to-LDS loads of 16 bytes (per-lane source address, destination = wave-uniform LDS base + 16 B x lane).
+// ONE buffer: take() reads the entry into registers at the top of an iteration, so the column is free for the next fetch()
+// straight away: 7 KB per wave.  What orders take()'s reads behind the fetch is the compiler's own wait for the LDS-DMA, and
+// it places that wait only where it believes the two may alias: NO __restrict__ on the pointer parameters of a function that
+// fetches (inlined, they become no-alias scopes, the reads count as independent of the DMA and are issued in front of the
+// vmcnt wait -- stale entries, wrong sums, no fault).  The rule covers the functions that fetch through this tile; the
+// lane-pair chain below loads through registers and keeps its qualifiers.
+template <class F>
+struct PrefetchTile {
+  static constexpr int CHUNKS = sizeof(Affine<F>) / 16;
+  typedef uint4 Column[CHUNKS][64];  // [chunk][lane], in LDS
+  uint4 (*col)[64];
+  uint32_t lane;
+  __device__ __forceinline__ void fetch(const Affine<F>* bases, uint32_t v) const {
+    const char* src = reinterpret_cast<const char*>(bases + (v & 0x7fffffffu));
+#pragma unroll
+    for (int q = 0; q < CHUNKS; q++)
+      __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + 16 * q), (lds_ptr_t)&col[q][0], 16, 0, 0);
+  }
+  __device__ __forceinline__ void take(Affine<F>& p) const {  // LDS -> registers; the compiler waits for the outstanding LDS-DMA first
+    uint4* d = reinterpret_cast<uint4*>(&p);
+#pragma unroll
+    for (int q = 0; q < CHUNKS; q++) d[q] = col[q][lane];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the reads have left the LDS: the buffer may be refilled
+  }
+};
+template <class F, bool FIRST_IS_AFFINE, uint32_t STRIDE>
+__device__ __forceinline__ bool accum_chain(XYZZ<F>& acc, const Affine<F>* bases, const uint32_t* sorted, uint32_t j, uint32_t rem,
+                                            const PrefetchTile<F>& tile) {
+  bool bad = false;
+  uint32_t v_cur = 0, v_next = 0;
+  if (rem > 0) {
+    v_cur = sorted[j];
+    tile.fetch(bases, v_cur);
+    if (rem > 1) v_next = sorted[j + STRIDE];
+  }
+  if constexpr (FIRST_IS_AFFINE) {
+    // The entry behind the first meets an accumulator that is still affine.  Lanes of a wave own buckets of near-equal load,
+    // so the wave takes this step together.  It is one peeled iteration of the loop below (same tile, same prefetch), not a
+    // loop of its own: an entry at infinity HERE (exceptional) leaves zz = zzz = 1 and the generic additions take over.  A
+    // search loop for "the next finite entry" spilt 144 - 228 bytes per lane.
+    bool paired = false;
+    if (rem > 0) {
+      Affine<F> p;
+      tile.take(p);
+      const uint32_t v = v_cur;
+      if (rem > 1) {
+        tile.fetch(bases, v_next);
+        v_cur = v_next;
+        if (rem > 2) v_next = sorted[j + 2 * STRIDE];
+      }
+      rem--;
+      j += STRIDE;
+      if (!affine_is_zero_words(p)) {
+        bad = !madd_affine_pair(acc, p, 0u - (v >> 31));
+        paired = true;
+      }
+    }
+    if (!paired) {
+      acc.zz = F::one();
+      acc.zzz = F::one();
+    }
+    if (bad) rem = 0;
+  }
+  // ONE exit behind the loop for both outcomes, and a count-down instead of (j, end): with a return to the redo list inside
+  // the loop or in front of it the register allocator spilt 12 - 124 bytes per lane around the pair step; this form needs
+  // no scratch in the light kernel (tests/test_cpu_host.py::test_kernel_register_budgets holds it to that).
+  for (; rem > 0; rem--, j += STRIDE) {
+    Affine<F> p;
+    tile.take(p);
+    const uint32_t v = v_cur;
+    if (rem > 1) {
+      tile.fetch(bases, v_next);
+      v_cur = v_next;
+      if (rem > 2) v_next = sorted[j + 2 * STRIDE];
+    }
+    if (affine_is_zero_words(p)) continue;
+    if (!madd_generic(acc, p, 0u - (v >> 31))) {
+      bad = true;
+      break;
+    }
+  }
+  return bad;
+}
+// (plain loads: runs once per chain)
+template <class F, uint32_t STRIDE>
+__device__ __forceinline__ bool accum_first(XYZZ<F>& acc, const Affine<F>* bases, const uint32_t* sorted, uint32_t& j, uint32_t& rem) {
+  bool have = false;
+  for (; rem > 0 && !have; rem--, j += STRIDE) {
+    const uint32_t v = sorted[j];
+    Affine<F> p = load_vec(bases + (v & 0x7fffffffu));
+    if (affine_is_zero_words(p)) continue;
+    if (v >> 31) p.y = p.y.neg();
+    acc.x = p.x;
+    acc.y = p.y;
+    have = true;
+  }
+  return have;
+}
+template <uint32_t STRIDE>
+__device__ __forceinline__ bool accum_first(XYZZ<Fq2P>& acc, const LanePair::Base* __restrict__ bases, const uint32_t* __restrict__ sorted,
+                                            uint32_t& j, uint32_t end, uint32_t comp) {
+  bool have = false;
+  for (; j < end && !have; j += STRIDE) {
+    Affine<Fq2P> p;
+    const uint32_t v = sorted[j];
+    if (LanePair::load_entry(bases, v, comp, p)) continue;
+    acc.x = p.x;
+    acc.y = (v >> 31) ? p.y.neg() : p.y;
+    have = true;
+  }
+  return have;
+}
+template <uint32_t STRIDE, bool FIRST_IS_AFFINE>
+__device__ __forceinline__ bool accum_chain(XYZZ<Fq2P>& acc, const LanePair::Base* __restrict__ bases, const uint32_t* __restrict__ sorted,
+                                            uint32_t j, uint32_t end, uint32_t comp) {
+  bool bad = false, paired = !FIRST_IS_AFFINE;
+  for (; j < end && !paired && !bad; j += STRIDE) {
+    Affine<Fq2P> p;
+    const uint32_t v = sorted[j];
+    if (LanePair::load_entry(bases, v, comp, p)) continue;
+    if (madd_affine_pair(acc, p, 0u - (v >> 31))) paired = true;  // pair-uniform (Fq2P::is_zero exchanges the halves)
+    else bad = true;
+  }
+  if (!paired) {  // one finite entry (or bad)
+    acc.zz = Fq2P::one();
+    acc.zzz = Fq2P::one();
+  }
+  for (; j < end && !bad; j += STRIDE) {
+    Affine<Fq2P> p;
+    const uint32_t v = sorted[j];
+    if (LanePair::load_entry(bases, v, comp, p)) continue;
+    if (!madd_generic(acc, p, 0u - (v >> 31))) bad = true;  // pair-uniform
+  }
+  return bad;
+}
+
+// G1 (and BN254 G1): thread per bucket, the one-lane chain over the bucket's entries.
 // What one launch accumulates: one MSM (table, bucket array, redo list + the digit sort it reads), or up to four MSMs of
 // the same shape, one per blockIdx.y -- the A, B1, L queries of a proof over the sort of z and the H query over the sort of
 // h.  One small proof uses the second form: 256-wave grids on separate streams did not start together (a kernel that
@@ -196,11 +466,12 @@ struct AccumArgs<F, true> {
 // reduction serves both MSMs.  A bucket the earlier MSM left EMPTY (exact zeros; probability e^-(mean load)) needs no
 // test of its own: with acc = (0, 0, 0, 0) the first addition computes P = x zz - X = 0, which is the "needs the complete
 // group law" exit below -- the bucket goes to the redo pass, whose complete addition starts from infinity.
-// (Any early exit through the redo list IN FRONT of the loop made the register allocator spill 120 dwords inside the
-// loop; with the one exit behind the count-down loop below this form spills 3, and the plain kernel needs 166 registers.)
-template <class F, int W, int BW, bool MULTI = false, bool INTO = false>
-__global__ void __launch_bounds__(64 * BW, W)
-k_accum_g1_nc(const AccumArgs<F, MULTI> args, uint32_t total_buckets) {
+// (Any early exit through the redo list IN FRONT of the chain made the register allocator spill 120 dwords inside its
+// loop; with the chain's one exit behind the loop this form spills 3, and the plain kernel needs no scratch.)
+// The body is a function because the occupancy-capped k_accum_g1_nc_w2 of the A/B library (msm_impl_exp.hpp) is the same
+// code under other attributes.
+template <class F, int BW, bool MULTI, bool INTO>
+__device__ __forceinline__ void accum_g1_nc_body(const AccumArgs<F, MULTI>& args, uint32_t total_buckets) {
   const Affine<F>* __restrict__ const bases = args.bases();
   XYZZ<F>* __restrict__ const buckets = args.buckets();
   uint32_t* __restrict__ const redo = args.redo();
@@ -209,27 +480,14 @@ k_accum_g1_nc(const AccumArgs<F, MULTI> args, uint32_t total_buckets) {
   const uint32_t* __restrict__ const perm = args.sort().perm;
   const uint32_t* __restrict__ const sorted = args.sort().sorted;
   const uint32_t heavy_thr = args.sort().heavy_thr;
-  constexpr int CHUNKS = sizeof(Affine<F>) / 16;  // 7 (BLS12-381 Fq), 5 (BN254 Fq)
-  __shared__ uint4 tile[BW][CHUNKS][64];          // [wave][chunk][lane]
+  __shared__ typename PrefetchTile<F>::Column tile[BW];  // [wave]
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const PrefetchTile<F> pf = {tile[threadIdx.x >> 6], threadIdx.x & 63};
   if (t >= total_buckets) return;
   const uint32_t b = perm[t];  // lanes of a wave own buckets of near-equal load
   const uint32_t cnt = count[b];
   if (cnt > heavy_thr) return;  // k_accum_heavy owns it
   const uint32_t beg = begin[b], end = beg + cnt;
-  auto fetch = [&](uint32_t v) {
-    const char* src = reinterpret_cast<const char*>(bases + (v & 0x7fffffffu));
-#pragma unroll
-    for (int q = 0; q < CHUNKS; q++)
-      __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + 16 * q), (lds_ptr_t)&tile[wave][q][0], 16, 0, 0);
-  };
-  auto take = [&](Affine<F>& p) {  // LDS -> registers; the compiler waits for the outstanding LDS-DMA first
-    uint4* d = reinterpret_cast<uint4*>(&p);
-#pragma unroll
-    for (int q = 0; q < CHUNKS; q++) d[q] = tile[wave][q][lane];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the reads have left the LDS: the buffer may be refilled
-  };
   XYZZ<F> acc;
   uint32_t j = beg;
   // first entry that is not the point at infinity starts the accumulator (plain loads: runs once per bucket)
@@ -242,74 +500,27 @@ k_accum_g1_nc(const AccumArgs<F, MULTI> args, uint32_t total_buckets) {
     Affine<F> p = load_vec(bases + (v & 0x7fffffffu));
     if (affine_is_zero_words(p)) continue;
     if constexpr (INTO) {
-      acc = load_vec(buckets + b);  // entry j itself is added by the loop below
+      acc = load_vec(buckets + b);  // entry j itself is added by the chain
       break;
     }
     if (v >> 31) p.y = p.y.neg();
     acc.x = p.x;
-    acc.y = p.y;  // (zz = zzz = 1 are set below, where the entry behind this one does not make them)
+    acc.y = p.y;  // (zz = zzz = 1 are the chain's to set, where the entry behind this one does not make them)
     j++;
     break;
   }
-  bool bad = false;  // doubling or cancellation met: the bucket goes to the redo list
-  uint32_t v_cur = 0, v_next = 0;
-  if (j < end) {
-    v_cur = sorted[j];
-    fetch(v_cur);
-    if (j + 1 < end) v_next = sorted[j + 1];
-  }
-  if constexpr (!INTO) {
-    // The entry behind the first meets an accumulator that is still affine: madd_affine_pair, 4M + 2S.  Lanes of a wave own
-    // buckets of near-equal load, so the wave takes this step together.  It is one peeled iteration of the loop below (same
-    // tile, same prefetch), not a loop of its own: an entry at infinity HERE (exceptional) leaves zz = zzz = 1 and the
-    // generic additions take over.  A search loop for "the next finite entry" spilt 144 - 228 bytes per lane.
-    bool paired = false;
-    if (j < end) {
-      Affine<F> p;
-      take(p);
-      const uint32_t v = v_cur;
-      if (j + 1 < end) {
-        fetch(v_next);
-        v_cur = v_next;
-        if (j + 2 < end) v_next = sorted[j + 2];
-      }
-      j++;
-      if (!affine_is_zero_words(p)) {
-        bad = !madd_affine_pair(acc, p, 0u - (v >> 31));
-        paired = true;
-      }
-    }
-    if (!paired) {
-      acc.zz = F::one();
-      acc.zzz = F::one();
-    }
-    if (bad) j = end;
-  }
-  // ONE exit behind the loop for both outcomes, and a count-down instead of (j, end): with a return to the redo list inside
-  // the loop or in front of it the register allocator spilt 12 - 124 bytes per lane around the pair step; this form needs
-  // 166 registers and no scratch (tests/test_cpu_host.py::test_kernel_register_budgets holds it to that).
-  const uint32_t* sp = sorted + j;
-  for (uint32_t rem = end - j; rem > 0; rem--, sp++) {
-    Affine<F> p;
-    take(p);
-    const uint32_t v = v_cur;
-    if (rem > 1) {
-      fetch(v_next);
-      v_cur = v_next;
-      if (rem > 2) v_next = sp[2];
-    }
-    if (affine_is_zero_words(p)) continue;
-    if (!madd_generic(acc, p, 0u - (v >> 31))) {
-      bad = true;
-      break;
-    }
-  }
-  if (bad) {
-    // k_accum_redo recomputes the bucket (INTO: from the value it still holds -- nothing has been written)
+  if (accum_chain<F, !INTO, 1>(acc, bases, sorted, j, end - j, pf)) {
+    // doubling or cancellation met: k_accum_redo recomputes the bucket (INTO: from the value it still holds -- nothing has
+    // been written)
     redo[1 + atomicAdd(redo, 1u)] = b;
     return;
   }
   store_vec(buckets + b, acc);
+}
+template <class F, int W, int BW, bool MULTI = false, bool INTO = false>
+__global__ void __launch_bounds__(64 * BW, W)
+k_accum_g1_nc(const AccumArgs<F, MULTI> args, uint32_t total_buckets) {
+  accum_g1_nc_body<F, BW, MULTI, INTO>(args, total_buckets);
 }
 #ifdef ZKMI_EXPERIMENTS
 }  // namespace zkmi
@@ -344,11 +555,38 @@ __device__ __forceinline__ bool add_generic(XYZZ<F>& a, const XYZZ<F>& o) {
   a.zzz = a.zzz * o.zzz * ppp;
   return true;
 }
+// The tail of a two-halves-per-bucket kernel (k_accum_g2_split2; written over the layout): half `sub` of a bucket has the partial sum acc (has: it met a finite entry;
+// bad: it met P + P or P - P).  The halves hold the same component L::LANES lanes apart; half 0 adds the two sums and stores
+// the bucket, or appends it to the redo list where either half or this addition needs the complete group law.
+template <class L>
+__device__ __forceinline__ void accum_split2_tail(typename L::P& acc, bool has, bool bad, uint32_t sub, uint32_t comp,
+                                                  typename L::Stored* buckets, uint32_t* redo, uint32_t b) {
+  const uint32_t flags = (has ? 1u : 0u) | (bad ? 2u : 0u);
+  const uint32_t pflags = (uint32_t)__shfl_xor((int)flags, L::LANES);
+  typename L::P o;
+  o.x = L::shfl_xor(acc.x, L::LANES);
+  o.y = L::shfl_xor(acc.y, L::LANES);
+  o.zz = L::shfl_xor(acc.zz, L::LANES);
+  o.zzz = L::shfl_xor(acc.zzz, L::LANES);
+  if (sub != 0) return;
+  bool redo_it = ((flags | pflags) & 2u) != 0;
+  if (!redo_it) {
+    if (has && (pflags & 1u)) redo_it = !add_generic(acc, o);  // uniform over the lanes of the point
+    else if (!has) acc = (pflags & 1u) ? o : L::P::infinity();
+  }
+  if (redo_it) {
+    if (comp == 0) redo[1 + atomicAdd(redo, 1u)] = b;  // k_accum_redo recomputes the bucket with the complete addition
+  } else {
+    L::store(buckets + b, acc, comp);
+  }
+}
 // Two adjacent lanes per bucket (even lane: entries beg, beg + 2, ...; odd lane: beg + 1, beg + 3, ...), the even lane adds
 // the two partial sums at the end.  For ONE small proof: its accumulation launch is 0.3 ms of chip time but lasts as long as
 // the fullest bucket's chain of dependent additions (25-35 of them, 0.65 ms); two lanes halve the chain (section 4.11).
 // Always the multi form (table / bucket array / redo list / sort per blockIdx.y); a doubling in either half or in the
-// final addition sends the bucket to the redo list like the one-lane kernel does.
+// final addition sends the bucket to the redo list like the one-lane kernel does.  (No pair step: every addition is generic.)
+// Spelt out, not a call site of accum_chain and accum_split2_tail: with either of them shared the BN254 instantiation needs
+// 149 - 167 registers instead of 148 (profiles/r13/accum_chain_refactor.txt), in every form tried.
 template <class F, int BW>
 __global__ void __launch_bounds__(64 * BW, 2)
 k_accum_g1_split2(const AccumArgs<F, true> args, uint32_t total_buckets) {
@@ -442,7 +680,7 @@ k_accum_g1_split2(const AccumArgs<F, true> args, uint32_t total_buckets) {
     store_vec(buckets + b, acc);
 }
 
-// G2, lane pair per bucket (see k_accum_g2_split)
+// G2, lane pair per bucket (see LanePair)
 template <int W, int BW>
 __global__ void __launch_bounds__(64 * BW, W)
 k_accum_g2_nc(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __restrict__ begin,
@@ -455,67 +693,17 @@ k_accum_g2_nc(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __restri
   const uint32_t b = perm[t];
   const uint32_t cnt = count[b];
   if (cnt > heavy_thr) return;
-  const uint32_t beg = begin[b], end = beg + cnt;
-  Fq28* dst = reinterpret_cast<Fq28*>(buckets + b);  // x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1
-  auto load_point = [&](uint32_t v, Affine<Fq2P>& p) {
-    const Fq28* src = reinterpret_cast<const Fq28*>(bases + (v & 0x7fffffffu));  // x.c0 x.c1 y.c0 y.c1
-    p.x.v = ld_comp(src + comp);
-    p.y.v = ld_comp(src + 2 + comp);
-    // infinity = all four components exact zeros: OR of this lane's words, combined with the partner's; the lowest
-    // limb of y decides for all but 2^-56 of the finite entries, the full test runs behind that (pair-uniform) branch
-    uint32_t o = (uint32_t)p.y.v.l[0];
-    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
-    if (o != 0) return false;
-#pragma unroll
-    for (int i = 0; i < Fq28::NL; i++) o |= (uint32_t)p.x.v.l[i] | (uint32_t)p.y.v.l[i];
-    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
-    return o == 0;  // (the digit's sign is applied by the caller: first point, or folded into madd_generic)
-  };
   XYZZ<Fq2P> acc;
-  uint32_t j = beg;
-  for (;; j++) {
-    if (j >= end) {
-      const Fq28 z = Fq28::zero();
-      for (int k = 0; k < 4; k++) st_comp(dst + 2 * k + comp, z);
-      return;
-    }
-    Affine<Fq2P> p;
-    const uint32_t v = sorted[j];
-    if (load_point(v, p)) continue;
-    acc.x = p.x;
-    acc.y = (v >> 31) ? p.y.neg() : p.y;
-    j++;
-    break;
+  uint32_t j = begin[b];
+  const uint32_t end = j + cnt;
+  bool bad = false;
+  if (accum_first<1>(acc, bases, sorted, j, end, comp)) bad = accum_chain<1, true>(acc, bases, sorted, j, end, comp);
+  else acc = XYZZ<Fq2P>::infinity();
+  if (bad) {
+    if (comp == 0) redo[1 + atomicAdd(redo, 1u)] = b;
+  } else {
+    LanePair::store(buckets + b, acc, comp);
   }
-  // the next finite entry meets an accumulator that is still affine: 4M + 2S (madd_affine_pair)
-  bool paired = false;
-  for (; j < end && !paired; j++) {
-    Affine<Fq2P> p;
-    const uint32_t v = sorted[j];
-    if (load_point(v, p)) continue;
-    if (!madd_affine_pair(acc, p, 0u - (v >> 31))) {  // pair-uniform (Fq2P::is_zero exchanges the halves)
-      if (comp == 0) redo[1 + atomicAdd(redo, 1u)] = b;
-      return;
-    }
-    paired = true;
-  }
-  if (!paired) {  // one finite entry
-    acc.zz = Fq2P::one();
-    acc.zzz = Fq2P::one();
-  }
-  for (; j < end; j++) {
-    Affine<Fq2P> p;
-    const uint32_t v = sorted[j];
-    if (load_point(v, p)) continue;
-    if (!madd_generic(acc, p, 0u - (v >> 31))) {  // pair-uniform
-      if (comp == 0) redo[1 + atomicAdd(redo, 1u)] = b;
-      return;
-    }
-  }
-  st_comp(dst + comp, acc.x.v);
-  st_comp(dst + 2 + comp, acc.y.v);
-  st_comp(dst + 4 + comp, acc.zz.v);
-  st_comp(dst + 6 + comp, acc.zzz.v);
 }
 
 // G2, TWO lane pairs per bucket (pair 0: entries beg, beg + 2, ...; pair 1: beg + 1, beg + 3, ...), pair 0 adds the two partial
@@ -534,160 +722,17 @@ k_accum_g2_split2(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __re
   const uint32_t b = perm[t];
   const uint32_t cnt = count[b];
   if (cnt > heavy_thr) return;
-  const uint32_t beg = begin[b], end = beg + cnt;
-  Fq28* dst = reinterpret_cast<Fq28*>(buckets + b);  // x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1
-  auto load_point = [&](uint32_t v, Affine<Fq2P>& p) {  // true = the point at infinity (see k_accum_g2_nc)
-    const Fq28* src = reinterpret_cast<const Fq28*>(bases + (v & 0x7fffffffu));
-    p.x.v = ld_comp(src + comp);
-    p.y.v = ld_comp(src + 2 + comp);
-    uint32_t o = (uint32_t)p.y.v.l[0];
-    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
-    if (o != 0) return false;
-#pragma unroll
-    for (int i = 0; i < Fq28::NL; i++) o |= (uint32_t)p.x.v.l[i] | (uint32_t)p.y.v.l[i];
-    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
-    return o == 0;
-  };
   XYZZ<Fq2P> acc = XYZZ<Fq2P>::infinity();
-  bool has = false, bad = false;
-  uint32_t j = beg + sub;
-  for (; j < end; j += 2) {  // this pair's first entry that is not the point at infinity starts its sum
-    Affine<Fq2P> p;
-    const uint32_t v = sorted[j];
-    if (load_point(v, p)) continue;
-    acc.x = p.x;
-    acc.y = (v >> 31) ? p.y.neg() : p.y;
-    acc.zz = Fq2P::one();
-    acc.zzz = Fq2P::one();
-    has = true;
-    j += 2;
-    break;
-  }
-  for (; j < end; j += 2) {
-    Affine<Fq2P> p;
-    const uint32_t v = sorted[j];
-    if (load_point(v, p)) continue;
-    if (!madd_generic(acc, p, 0u - (v >> 31))) {  // pair-uniform
-      bad = true;
-      break;
-    }
-  }
-  // the other pair's state and partial sum (lane ^ 2: the same component of the other pair)
-  const uint32_t flags = (has ? 1u : 0u) | (bad ? 2u : 0u);
-  const uint32_t pflags = (uint32_t)__shfl_xor((int)flags, 2);
-  XYZZ<Fq2P> o;
-#pragma unroll
-  for (int i = 0; i < Fq28::NL; i++) {
-    o.x.v.l[i] = __shfl_xor(acc.x.v.l[i], 2);
-    o.y.v.l[i] = __shfl_xor(acc.y.v.l[i], 2);
-    o.zz.v.l[i] = __shfl_xor(acc.zz.v.l[i], 2);
-    o.zzz.v.l[i] = __shfl_xor(acc.zzz.v.l[i], 2);
-  }
-  if (sub != 0) return;
-  bool redo_it = ((flags | pflags) & 2u) != 0;
-  if (!redo_it) {
-    if (has && (pflags & 1u)) redo_it = !add_generic(acc, o);  // pair-uniform
-    else if (!has) acc = (pflags & 1u) ? o : XYZZ<Fq2P>::infinity();
-  }
-  if (redo_it) {
-    if (comp == 0) redo[1 + atomicAdd(redo, 1u)] = b;  // k_accum_redo recomputes the bucket with the complete addition
-  } else {
-    st_comp(dst + comp, acc.x.v);
-    st_comp(dst + 2 + comp, acc.y.v);
-    st_comp(dst + 4 + comp, acc.zz.v);
-    st_comp(dst + 6 + comp, acc.zzz.v);
-  }
+  const uint32_t beg = begin[b], end = beg + cnt;
+  uint32_t j = beg + sub;  // this pair's entries: every second one
+  bool bad = false;
+  acc.zz = Fq2P::one();  // (in front of the search: behind it, 2 registers more; the tail does not read the sum of a half without a finite entry)
+  acc.zzz = Fq2P::one();
+  const bool has = accum_first<2>(acc, bases, sorted, j, end, comp);
+  if (has) bad = accum_chain<2, false>(acc, bases, sorted, j, end, comp);
+  accum_split2_tail<LanePair>(acc, has, bad, sub, comp, buckets, redo, b);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Lane layouts of the reduction-side kernels (redo, heavy buckets, segment sums, tree sums).  Each of these algorithms has
-// ONE body, written over a layout L that says how a point lies across lanes; the __global__ entry points behind each body
-// are one call each and differ in layout and __launch_bounds__ only.
-//   OneLane<F>  a lane per point (G1, BN254 G1; the unsplit G2 tree sum of the A/B library)
-//   LanePair    a lane pair per G2 point, one Fq2 component per lane (field28.hpp Fq2P, see k_accum_g2_nc): per-lane state
-//               is that of a G1 addition.  The unsplit forms are 330-register kernels with 45-75 us per dependent addition:
-//               0.8 ms for one 600-point bucket of a 2^14 proof, on the critical path of the G2 reduction; and 0.1 ms to
-//               place an EMPTY redo kernel.
-// Memory layouts are the unsplit ones for both.  Thread i (of the workgroup, or of the grid) is lane `comp` = i % LANES of
-// point i / LANES, and every branch around an addition is uniform over the lanes of a point.
-// ---------------------------------------------------------------------------------------------
-template <class F>
-struct OneLane {
-  typedef XYZZ<F> Stored;                             // the point in memory
-  typedef XYZZ<F> P;                                  // what a lane holds of it
-  typedef XYZZ<typename HostFieldOf<F>::type> Host;   // the host-representation point
-  typedef Affine<F> Base;                             // a table entry in memory
-  static constexpr uint32_t LANES = 1;
-  __device__ __forceinline__ static P load(const Stored* p, uint32_t) { return load_vec(p); }
-  __device__ __forceinline__ static void store(Stored* p, const P& v, uint32_t) { store_vec(p, v); }
-  __device__ __forceinline__ static void store_host(Host* p, const P& v, uint32_t) {
-    const Host o = {fq_from_fq28(v.x), fq_from_fq28(v.y), fq_from_fq28(v.zz), fq_from_fq28(v.zzz)};
-    store_vec(p, o);
-  }
-  // the table entry of a sorted[] word, negated where the word's sign bit is set
-  __device__ __forceinline__ static Affine<F> load_affine(const Base* bases, uint32_t v, uint32_t) {
-    Affine<F> p = load_vec(bases + (v & 0x7fffffffu));
-    if (v >> 31) p.y = p.y.neg();
-    return p;
-  }
-  // heavy_marker() left by k_accum_heavy_nc: "infinity" with zzz word 0 set; *empty: all zz words zero, marker or not
-  __device__ __forceinline__ static bool is_marker(const P& v, uint32_t, bool* empty) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int i = 0; i < F::NL; i++) o |= (uint32_t)v.zz.l[i];
-    *empty = o == 0;
-    return o == 0 && v.zzz.l[0] == 1;
-  }
-};
-struct LanePair {
-  typedef XYZZ<Fq2_28> Stored;  // x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1: lane `comp` reads / writes every second one
-  typedef XYZZ<Fq2P> P;
-  typedef XYZZ<Fq2> Host;
-  typedef Affine<Fq2_28> Base;
-  static constexpr uint32_t LANES = 2;
-  __device__ __forceinline__ static P load(const Stored* p, uint32_t comp) {
-    const Fq28* s = reinterpret_cast<const Fq28*>(p);
-    P r;
-    r.x.v = ld_comp(s + comp);
-    r.y.v = ld_comp(s + 2 + comp);
-    r.zz.v = ld_comp(s + 4 + comp);
-    r.zzz.v = ld_comp(s + 6 + comp);
-    return r;
-  }
-  __device__ __forceinline__ static void store(Stored* p, const P& v, uint32_t comp) {
-    Fq28* d = reinterpret_cast<Fq28*>(p);
-    st_comp(d + comp, v.x.v);
-    st_comp(d + 2 + comp, v.y.v);
-    st_comp(d + 4 + comp, v.zz.v);
-    st_comp(d + 6 + comp, v.zzz.v);
-  }
-  __device__ __forceinline__ static void store_host(Host* p, const P& v, uint32_t comp) {
-    Fq* d = reinterpret_cast<Fq*>(p);
-    d[comp] = fq_from_fq28(v.x.v);
-    d[2 + comp] = fq_from_fq28(v.y.v);
-    d[4 + comp] = fq_from_fq28(v.zz.v);
-    d[6 + comp] = fq_from_fq28(v.zzz.v);
-  }
-  __device__ __forceinline__ static Affine<Fq2P> load_affine(const Base* bases, uint32_t v, uint32_t comp) {
-    const Fq28* src = reinterpret_cast<const Fq28*>(bases + (v & 0x7fffffffu));  // x.c0 x.c1 y.c0 y.c1
-    Affine<Fq2P> p;
-    p.x.v = ld_comp(src + comp);
-    p.y.v = ld_comp(src + 2 + comp);
-    if (v >> 31) p.y = p.y.neg();
-    return p;
-  }
-  // the marker of k_accum_heavy_nc_g2 is zzz.c0 word 0: both tests ORed over the pair with one DPP swap each
-  __device__ __forceinline__ static bool is_marker(const P& v, uint32_t comp, bool* empty) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int i = 0; i < Fq28::NL; i++) o |= (uint32_t)v.zz.v.l[i];
-    uint32_t mk = (comp == 0 && v.zzz.v.l[0] == 1) ? 1u : 0u;
-    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
-    mk |= (uint32_t)__builtin_amdgcn_mov_dpp((int)mk, 0xB1, 0xF, 0xF, true);
-    *empty = o == 0;
-    return o == 0 && mk == 1;
-  }
-};
 // LDS tree over the npt points a workgroup holds (a power of two; sh: npt x Stored): the sum ends in the lanes of point 0
 template <class L>
 __device__ __forceinline__ typename L::P lanes_tree_sum(typename L::P acc, typename L::Stored* sh, uint32_t pt, uint32_t npt, uint32_t comp) {
@@ -876,98 +921,35 @@ template <class F, int W>
 __global__ void __launch_bounds__(64, W)
 k_accum_heavy_nc(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ hplan,
                  XYZZ<F>* __restrict__ pool) {
-  constexpr int CHUNKS = sizeof(Affine<F>) / 16;
-  __shared__ uint4 tile[CHUNKS][64];
+  __shared__ typename PrefetchTile<F>::Column tile;
   if (hplan[3] != 0) return;  // point mode: k_accum_heavy takes the list
   const uint32_t n_items = hplan[0], pl = hplan[1], n_ent = hplan[2];
   const uint32_t* __restrict__ const ent = hplan + 4;
   const uint32_t lane = threadIdx.x;
-  auto fetch = [&](uint32_t v) {
-    const char* src = reinterpret_cast<const char*>(bases + (v & 0x7fffffffu));
-#pragma unroll
-    for (int q = 0; q < CHUNKS; q++) __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + 16 * q), (lds_ptr_t)&tile[q][0], 16, 0, 0);
-  };
-  auto take = [&](Affine<F>& p) {
-    uint4* d = reinterpret_cast<uint4*>(&p);
-#pragma unroll
-    for (int q = 0; q < CHUNKS; q++) d[q] = tile[q][lane];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
+  const PrefetchTile<F> pf = {tile, lane};
   for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
     const uint32_t e = heavy_plan_entry(ent, n_ent, it);
     const uint32_t beg = ent[4 * e + 1], cnt = ent[4 * e + 2], first = ent[4 * e + 3];
     const uint32_t w0 = beg + (it - first) * 64u * pl;
     const uint32_t w1 = (w0 + 64u * pl < beg + cnt) ? w0 + 64u * pl : beg + cnt;
-    XYZZ<F>* const dst = pool + (size_t)it * 64 + lane;
     XYZZ<F> acc;
-    uint32_t j = w0 + lane;
-    bool have = false;
-    for (; j < w1; j += 64) {  // the lane's first entry that is not the point at infinity starts its sum
-      const uint32_t v = sorted[j];
-      Affine<F> p = load_vec(bases + (v & 0x7fffffffu));
-      if (affine_is_zero_words(p)) continue;
-      if (v >> 31) p.y = p.y.neg();
-      acc.x = p.x;
-      acc.y = p.y;
-      have = true;
-      j += 64;
-      break;
-    }
-    if (!have) {
-      store_vec(dst, XYZZ<F>::infinity());
+    uint32_t j = w0 + lane;  // the lane's entries: w0 + lane, + 64, ... below w1
+    uint32_t rem = w0 + lane < w1 ? (w1 - w0 - lane + 63) / 64 : 0u;
+    if (!accum_first<F, 64>(acc, bases, sorted, j, rem)) {
+      store_vec(pool + (size_t)it * 64 + lane, XYZZ<F>::infinity());
       continue;
     }
-    uint32_t v_cur = 0, v_next = 0;
-    if (j < w1) {
-      v_cur = sorted[j];
-      fetch(v_cur);
-      if (j + 64 < w1) v_next = sorted[j + 64];
-    }
-    // the lane's entry behind the first meets a sum that is still affine: madd_affine_pair (k_accum_g1_nc's peeled iteration)
-    bool bad = false, paired = false;
-    if (j < w1) {
-      Affine<F> p;
-      take(p);
-      const uint32_t v = v_cur;
-      if (j + 64 < w1) {
-        fetch(v_next);
-        v_cur = v_next;
-        if (j + 128 < w1) v_next = sorted[j + 128];
-      }
-      j += 64;
-      if (!affine_is_zero_words(p)) {
-        bad = !madd_affine_pair(acc, p, 0u - (v >> 31));
-        paired = true;
-      }
-    }
-    if (!paired) {
-      acc.zz = F::one();
-      acc.zzz = F::one();
-    }
-    if (bad) j = w1;  // k_accum_heavy recomputes this lane's <= PL points with the complete law
-    for (; j < w1; j += 64) {
-      Affine<F> p;
-      take(p);
-      const uint32_t v = v_cur;
-      if (j + 64 < w1) {
-        fetch(v_next);
-        v_cur = v_next;
-        if (j + 128 < w1) v_next = sorted[j + 128];
-      }
-      if (affine_is_zero_words(p)) continue;
-      if (!madd_generic(acc, p, 0u - (v >> 31))) {
-        bad = true;
-        break;
-      }
-    }
+    // the light kernel's chain; k_accum_heavy recomputes the <= PL points of a lane that met P + P with the complete law
+    const bool bad = accum_chain<F, true, 64>(acc, bases, sorted, j, rem, pf);
+    XYZZ<F>* const dst = pool + (size_t)it * 64 + lane;
     if (bad) store_vec(dst, heavy_marker<F>());
     else store_vec(dst, acc);
-    // (a lane that left the loop early still has a direct-to-LDS load in flight into its own column of the tile: the next
+    // (a lane that left the chain early still has a direct-to-LDS load in flight into its own column of the tile: the next
     // item's first fetch into the same column is ordered behind it, and take() waits for both)
   }
 }
 
-// G2: 32 lane pairs per wave-item (field28.hpp Fq2P), the light G2 kernel's loop
+// G2: 32 lane pairs per wave-item (field28.hpp Fq2P), the light G2 kernel's chain
 template <int W>
 __global__ void __launch_bounds__(64, W)
 k_accum_heavy_nc_g2(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ hplan,
@@ -976,72 +958,19 @@ k_accum_heavy_nc_g2(const Affine<Fq2_28>* __restrict__ bases, const uint32_t* __
   const uint32_t n_items = hplan[0], pl = hplan[1], n_ent = hplan[2];
   const uint32_t* __restrict__ const ent = hplan + 4;
   const uint32_t pair = threadIdx.x >> 1, comp = threadIdx.x & 1u;
-  auto load_point = [&](uint32_t v, Affine<Fq2P>& p) {  // true = the point at infinity (all four components exact zeros)
-    const Fq28* src = reinterpret_cast<const Fq28*>(bases + (v & 0x7fffffffu));
-    p.x.v = ld_comp(src + comp);
-    p.y.v = ld_comp(src + 2 + comp);
-    uint32_t o = (uint32_t)p.y.v.l[0];
-    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
-    if (o != 0) return false;
-#pragma unroll
-    for (int i = 0; i < Fq28::NL; i++) o |= (uint32_t)p.x.v.l[i] | (uint32_t)p.y.v.l[i];
-    o |= (uint32_t)__builtin_amdgcn_mov_dpp((int)o, 0xB1, 0xF, 0xF, true);
-    return o == 0;
-  };
   for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
     const uint32_t e = heavy_plan_entry(ent, n_ent, it);
     const uint32_t beg = ent[4 * e + 1], cnt = ent[4 * e + 2], first = ent[4 * e + 3];
     const uint32_t w0 = beg + (it - first) * 32u * pl;
     const uint32_t w1 = (w0 + 32u * pl < beg + cnt) ? w0 + 32u * pl : beg + cnt;
-    Fq28* const dst = reinterpret_cast<Fq28*>(pool + (size_t)it * 32 + pair);  // x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1
+    XYZZ<Fq2_28>* const dst = pool + (size_t)it * 32 + pair;
     XYZZ<Fq2P> acc;
-    uint32_t j = w0 + pair;
-    bool have = false, bad = false;
-    for (; j < w1; j += 32) {
-      Affine<Fq2P> p;
-      const uint32_t v = sorted[j];
-      if (load_point(v, p)) continue;
-      acc.x = p.x;
-      acc.y = (v >> 31) ? p.y.neg() : p.y;
-      have = true;
-      j += 32;
-      break;
-    }
-    if (have) {
-      // the pair's next finite entry meets a sum that is still affine: 4M + 2S (madd_affine_pair)
-      bool paired = false;
-      for (; j < w1 && !paired && !bad; j += 32) {
-        Affine<Fq2P> p;
-        const uint32_t v = sorted[j];
-        if (load_point(v, p)) continue;
-        if (madd_affine_pair(acc, p, 0u - (v >> 31))) paired = true;  // pair-uniform
-        else bad = true;
-      }
-      if (!paired) {  // one finite entry (or bad: the marker is stored below)
-        acc.zz = Fq2P::one();
-        acc.zzz = Fq2P::one();
-      }
-      for (; j < w1 && !bad; j += 32) {
-        Affine<Fq2P> p;
-        const uint32_t v = sorted[j];
-        if (load_point(v, p)) continue;
-        if (!madd_generic(acc, p, 0u - (v >> 31))) bad = true;  // pair-uniform
-      }
-    }
-    if (!have || bad) {
-      const Fq28 z = Fq28::zero();
-      Fq28 mk = z;
-      mk.l[0] = (bad && comp == 0) ? 1 : 0;  // marker: zzz.c0 word 0 (k_accum_heavy_g2_split recomputes the pair's points)
-      st_comp(dst + comp, z);
-      st_comp(dst + 2 + comp, z);
-      st_comp(dst + 4 + comp, z);
-      st_comp(dst + 6 + comp, mk);
-    } else {
-      st_comp(dst + comp, acc.x.v);
-      st_comp(dst + 2 + comp, acc.y.v);
-      st_comp(dst + 4 + comp, acc.zz.v);
-      st_comp(dst + 6 + comp, acc.zzz.v);
-    }
+    uint32_t j = w0 + pair;  // the pair's entries: w0 + pair, + 32, ... below w1
+    bool bad = false;
+    const bool have = accum_first<32>(acc, bases, sorted, j, w1, comp);
+    if (have) bad = accum_chain<32, true>(acc, bases, sorted, j, w1, comp);
+    if (!have || bad) LanePair::store_marker(dst, bad, comp);
+    else LanePair::store(dst, acc, comp);
   }
 }
 

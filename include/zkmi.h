@@ -581,8 +581,9 @@ int32_t zkmi_pk_check(zkmi_ctx* ctx, const zkmi_pk* pk, int32_t checks, uint64_t
  * [tau^i]G1, [tau^i]G2, [alpha tau^i]G1, [beta tau^i]G1, [beta]G2 -- resident and checked on the device, and the
  * transform that turns powers of tau into the Lagrange basis [L_i(tau)]G "in the exponent"; then the circuit-specific
  * step: zkmi_groth16_setup_from_srs derives a relation's key from the transcript (the sums over the R1CS columns and the
- * h query, on the device) and zkmi_pk_contribute applies a phase-2 contribution to delta.  Verifying somebody else's
- * contribution (the ratio checks by pairing) and the same-ratio checks of the transcript itself are the caller's. */
+ * h query, on the device) and zkmi_pk_contribute applies a phase-2 contribution to delta.  The checks a ceremony
+ * verifier makes run here too: zkmi_srs_verify holds a transcript to the same-ratio equations, and
+ * zkmi_pk_verify_contribution holds a contributed key to its predecessor (below). */
 /* In-place transform of 2^log_n points in HBM, affine WIRE form (all zero = infinity), natural order in and out:
  * out[i] = sum_k w^(ik) in[k] (forward), out[i] = N^-1 sum_k w^(-ik) in[k] (inverse), w = the root zkmi_ntt_fr uses.
  * The points must be in the r-order subgroup (caller's duty, as for zkmi_pairing_product_dev); a coordinate >= p is
@@ -596,8 +597,9 @@ typedef struct zkmi_srs zkmi_srs;
  *   beta_g2 one point.  Also refused (ZKMI_ERR_NON_CANONICAL): tau_g1[0] != G1 generator, tau_g2[0] != G2 generator.
  * out_where (optional): [0] = section of the refused point (0 tau_g1, 1 tau_g2, 2 alpha_tau_g1, 3 beta_tau_g1,
  * 4 beta_g2), [1] = index; UINT64_MAX twice when no point was refused.  A refused transcript leaves *out NULL.
- * NOT checked: that the arrays are consistent powers of ONE tau, alpha and beta -- the pairing "same ratio" checks of a
- * ceremony verifier.  A transcript that fails those yields a key that proves nothing; verify it before it gets here. */
+ * NOT checked by the load: that the arrays are consistent powers of ONE tau, alpha and beta -- the pairing "same ratio"
+ * checks of a ceremony verifier.  A transcript that fails those yields a key that proves nothing: run zkmi_srs_verify
+ * on the handle before a key is derived from it.  The handle remembers `checks`. */
 int32_t zkmi_srs_load(zkmi_ctx* ctx, int32_t encoding, int32_t checks,
                       const uint8_t* tau_g1, uint64_t n_tau_g1, const uint8_t* tau_g2, uint64_t n_tau_g2,
                       const uint8_t* alpha_tau_g1, const uint8_t* beta_tau_g1, uint64_t n_ab,
@@ -623,6 +625,55 @@ int32_t zkmi_groth16_setup_from_srs(zkmi_ctx* ctx, const zkmi_r1cs* r1cs, const 
  * ZKMI_ERR_BAD_ARG; a refused call leaves the key untouched.  Waits for everything queued on the context first. */
 int32_t zkmi_pk_contribute(zkmi_ctx* ctx, zkmi_pk* pk, const uint8_t d[32], uint8_t out_delta_g1[96],
                            uint8_t out_delta_g2[192]);
+
+/* ---- verifying a ceremony: random linear combinations with weights derived on the device ------------------------ *
+ * The weight of index i in domain `dom` under a 32-byte seed is
+ *   w(seed, dom, i) = the first 16 bytes of SHA-256(seed[32] | LE32(dom) | LE64(i)), read as a little-endian 128-bit integer
+ * (one SHA-256 block per weight, one lane per index).  Domains: the section numbers of zkmi_srs_load in phase 1 (0 tau_g1,
+ * 1 tau_g2, 2 alpha_tau_g1, 3 beta_tau_g1), 16 + the query number of zkmi_pk_export_query in phase 2 (19 h, 20 l, the
+ * index counted as that export counts it).  Every equation below is a random linear combination of the per-index
+ * equations under these weights: for a seed the prover of the data did not choose (NULL draws one from the OS), data
+ * that breaks a relation passes the equation that names it with probability at most 2^-128.
+ *
+ * m points in HBM, affine WIRE form (4-byte aligned), in the r-order subgroup (caller's duty):
+ *   out_lo = sum_{i=0}^{m-2} w(seed,dom,i) * P[i],   out_hi = sum_{i=0}^{m-2} w(seed,dom,i) * P[i+1]
+ * m = 1: both infinity (all-zero wire form).  m = 0 or a NULL argument: ZKMI_ERR_BAD_ARG; a coordinate >= p:
+ * ZKMI_ERR_NON_CANONICAL.  Two runs of the library's MSM over one conversion of the array.  Waits for the results. */
+int32_t zkmi_g1_points_adjacent_sums_dev(zkmi_ctx* ctx, const void* d_points, uint64_t m, const uint8_t seed[32],
+                                         uint32_t dom, uint8_t out_lo[96], uint8_t out_hi[96]);
+int32_t zkmi_g2_points_adjacent_sums_dev(zkmi_ctx* ctx, const void* d_points, uint64_t m, const uint8_t seed[32],
+                                         uint32_t dom, uint8_t out_lo[192], uint8_t out_hi[192]);
+/* The same-ratio checks of a resident transcript, each its own two-pair product (lo / hi: the adjacent sums of a section): */
+#define ZKMI_SRS_BAD_TAU_G1    1u   /* e(hi(tau_g1), G2)        != e(lo(tau_g1), tau_g2[1]) */
+#define ZKMI_SRS_BAD_TAU_G2    2u   /* e(tau_g1[1], lo(tau_g2)) != e(G1, hi(tau_g2))   (i = 0 ties tau in G1 to tau in G2) */
+#define ZKMI_SRS_BAD_ALPHA     4u   /* e(hi(alpha_tau_g1), G2)  != e(lo(alpha_tau_g1), tau_g2[1]) */
+#define ZKMI_SRS_BAD_BETA      8u   /* the same for beta_tau_g1 */
+#define ZKMI_SRS_BAD_BETA_G2  16u   /* e(beta_tau_g1[0], G2)    != e(G1, beta_g2) */
+#define ZKMI_SRS_DEGENERATE   32u   /* tau_g1[1], tau_g2[1], alpha_tau_g1[0], beta_tau_g1[0] or beta_g2 is infinity,
+                                       or n_tau_g1 < 2 or n_tau_g2 < 2 (no tau to compare against) */
+/* ZKMI_OK with *out_failed = 0 for a consistent transcript; ZKMI_ERR_VERIFICATION with the mask of every failed check
+ * otherwise; ZKMI_ERR_BAD_ARG for NULLs or a transcript of another context or device.  A chain of one point (n_ab = 1)
+ * holds: both sums are infinity.  DEGENERATE is reported alone, the equations are not evaluated then; a transcript
+ * with no power of tau at all (all three lengths 1, the domain of size 1) is not degenerate: there is nothing to
+ * compare, and only the anchors and BETA_G2 are checked.
+ * The sums are only sound over points of the r-order subgroup (a component of small order could cancel under the
+ * pairing), so a transcript that was not loaded under ZKMI_CHECK_SUBGROUP is refused with ZKMI_ERR_BAD_ARG;
+ * zkmi_srs_generate counts as fully checked.  seed NULL: drawn from the OS, as zkmi_groth16_verify_batch draws its
+ * weights.  Waits for everything queued on the context first; the transcript is only read. */
+int32_t zkmi_srs_verify(zkmi_ctx* ctx, const zkmi_srs* srs, const uint8_t seed[32], uint32_t* out_failed);
+/* One phase-2 contribution, `after` against `before` (which may itself be the result of earlier contributions: a
+ * verifier chains calls): */
+#define ZKMI_PK2_FIXED_PART_DIFFERS 1u  /* alpha_g1, beta_g1, beta_g2, or any entry of the a, b_g1, b_g2 queries */
+#define ZKMI_PK2_BAD_DELTA          2u  /* delta' infinity, or e(delta'_g1, G2) != e(G1, delta'_g2) */
+#define ZKMI_PK2_BAD_H              4u  /* e(sum w_i h'_i, delta'_g2) != e(sum w_i h_i, delta_g2),  i < N - 1 */
+#define ZKMI_PK2_BAD_L              8u  /* the same over l[n_pub .. n_vars) */
+/* Both keys resident on ctx and idle; the call waits for everything queued on the context first and only reads them.
+ * ZKMI_OK with *out_failed = 0, ZKMI_ERR_VERIFICATION with the mask of every failed check, ZKMI_ERR_BAD_ARG for NULLs,
+ * keys of another context, or keys of different shape (n_vars, n_pub, log_n).  Precondition: the points of both keys
+ * are in the r-order subgroup (zkmi_pk_check, zkmi_ark_pk_load_validated, or keys this library made).  The verifying
+ * key's bytes are the caller's to compare, as they are the caller's to patch.  seed NULL: drawn from the OS. */
+int32_t zkmi_pk_verify_contribution(zkmi_ctx* ctx, const zkmi_pk* before, const zkmi_pk* after, const uint8_t seed[32],
+                                    uint32_t* out_failed);
 
 /* ---- row a12: the reference's prove/verify surface ------------------------ */
 #define ZKMI_MERKLE_TREE_DEPTH 10 /* shielder/mocked_zk/src/lib.rs:16 */

@@ -176,6 +176,13 @@ int32_t zkmi_selftest_setup_columns_host(const zkmi_r1cs* r1cs, const uint8_t to
 /* The last zkmi_groth16_setup_from_srs of this library, in ms of host clock (every phase ends in a stream wait):
  * [0] Lagrange transforms, [1] column sums, [2] h query.  One global, last call wins; the product library records nothing. */
 int32_t zkmi_setup_from_srs_phases(double out_ms[3]);
+/* ceremony.hip: w(seed, dom, i) for i = first .. first + count - 1 through the body k_rlc_weights runs, in a host loop:
+ * out16 = count x 16 bytes, each the little-endian weight (include/zkmi.h: the first 16 bytes of the SHA-256 digest). */
+int32_t zkmi_selftest_rlc_weights_host(const uint8_t seed[32], uint32_t dom, uint64_t first, uint64_t count, uint8_t* out16);
+/* The last zkmi_srs_verify / zkmi_pk_verify_contribution of this library, in ms of host clock (every phase ends in a stream
+ * wait): [0] weights, [1] conversion to the MSM's base form, [2] MSMs, [3] pairing products.  One global, last call wins;
+ * the product library records nothing. */
+int32_t zkmi_ceremony_phases(double out_ms[4]);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,15 @@ extern "C" {
     pub fn zkmi_groth16_setup_from_srs(ctx: *mut zkmi_ctx, r1cs: *const zkmi_r1cs, srs: *const zkmi_srs, out_pk: *mut *mut zkmi_pk,
                                        vk_out: *mut u8, vk_cap: u64) -> i32;
     pub fn zkmi_pk_contribute(ctx: *mut zkmi_ctx, pk: *mut zkmi_pk, d: *const u8, out_delta_g1: *mut u8, out_delta_g2: *mut u8) -> i32;
+    // verifying a ceremony: the same-ratio checks of a transcript and of a contribution (seed: 32 bytes or null = drawn;
+    // out_failed: the ZKMI_SRS_* / ZKMI_PK2_* mask), and the adjacent weighted sums below them
+    pub fn zkmi_srs_verify(ctx: *mut zkmi_ctx, srs: *const zkmi_srs, seed: *const u8, out_failed: *mut u32) -> i32;
+    pub fn zkmi_pk_verify_contribution(ctx: *mut zkmi_ctx, before: *const zkmi_pk, after: *const zkmi_pk, seed: *const u8,
+                                       out_failed: *mut u32) -> i32;
+    pub fn zkmi_g1_points_adjacent_sums_dev(ctx: *mut zkmi_ctx, d_points: *const core::ffi::c_void, m: u64, seed: *const u8, dom: u32,
+                                            out_lo: *mut u8, out_hi: *mut u8) -> i32;
+    pub fn zkmi_g2_points_adjacent_sums_dev(ctx: *mut zkmi_ctx, d_points: *const core::ffi::c_void, m: u64, seed: *const u8, dom: u32,
+                                            out_lo: *mut u8, out_hi: *mut u8) -> i32;
     pub fn zkmi_ark_vk_read(buf: *const u8, len: u64, compressed: i32, out_vk: *mut u8, vk_cap: u64, out_n_pub: *mut u32, out_consumed: *mut u64) -> i32;
     pub fn zkmi_pk_shape(pk: *const zkmi_pk, n_vars: *mut u32, n_pub: *mut u32, log_n: *mut u32) -> i32;
     pub fn zkmi_host_info(out: *mut u32) -> i32;

@@ -24,4 +24,16 @@ from .binding import (  # noqa: F401
     PT_BAD_ENCODING,
     PT_NOT_ON_CURVE,
     PT_NOT_IN_SUBGROUP,
+    SRS_BAD_TAU_G1,
+    SRS_BAD_TAU_G2,
+    SRS_BAD_ALPHA,
+    SRS_BAD_BETA,
+    SRS_BAD_BETA_G2,
+    SRS_DEGENERATE,
+    PK2_FIXED_PART_DIFFERS,
+    PK2_BAD_DELTA,
+    PK2_BAD_H,
+    PK2_BAD_L,
+    Srs,
+    ProvingKey,
 )

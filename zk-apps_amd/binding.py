@@ -35,6 +35,9 @@ ENC_WIRE, ENC_ZCASH_COMPRESSED, ENC_ZCASH_UNCOMPRESSED = 0, 1, 2
 CHECK_CURVE, CHECK_SUBGROUP = 1, 2
 PT_OK, PT_BAD_ENCODING, PT_NOT_ON_CURVE, PT_NOT_IN_SUBGROUP = 0, 1, 2, 3
 NO_INDEX = (1 << 64) - 1
+# masks of Context.srs_verify / Context.pk_verify_contribution (include/zkmi.h)
+SRS_BAD_TAU_G1, SRS_BAD_TAU_G2, SRS_BAD_ALPHA, SRS_BAD_BETA, SRS_BAD_BETA_G2, SRS_DEGENERATE = 1, 2, 4, 8, 16, 32
+PK2_FIXED_PART_DIFFERS, PK2_BAD_DELTA, PK2_BAD_H, PK2_BAD_L = 1, 2, 4, 8
 MERKLE_TREE_DEPTH = 10
 MAX_TREE_HEIGHT = 32
 TOKENS_NUMBER = 2
@@ -552,6 +555,14 @@ class Zkmi:
         self._chk(self.tlib.zkmi_selftest_setup_columns_host(r1cs.h, _buf(toxic3), C.c_int32(which), out))
         return bytes(out)
 
+    def selftest_rlc_weights_host(self, seed, dom, first, count):
+        """Testing library: w(seed, dom, i) for i in [first, first + count) through the body k_rlc_weights runs, in a host
+        loop -> count x 16 bytes (little-endian weights)."""
+        assert len(seed) == 32
+        out = (C.c_uint8 * (16 * max(1, count)))()
+        self._chk(self.tlib.zkmi_selftest_rlc_weights_host(_buf(seed), C.c_uint32(dom), C.c_uint64(first), C.c_uint64(count), out))
+        return bytes(out)[: 16 * count]
+
     # ---- reference prove/verify surface (mocked_zk mirror) -------------------
     def account_new(self, tokens):
         arr = (Scalar * TOKENS_NUMBER)(*[scalar(t) for t in tokens])
@@ -1050,6 +1061,47 @@ class Context:
         self._chk(self.lib.zkmi_srs_generate(self.h, _buf(toxic), C.c_uint32(log_n), C.byref(h)))
         return Srs(self, h)
 
+    def _verdict(self, rc, failed):
+        """(ok, failed_mask) of a verification call: a failed check is an answer, every other refusal raises."""
+        if rc == -5:
+            return False, int(failed.value)
+        self._chk(rc)
+        return True, int(failed.value)
+
+    def srs_verify(self, srs, seed=None):
+        """zkmi_srs_verify: the same-ratio checks of a resident transcript under the weights of `seed` (32 bytes; None: drawn
+        by the library) -> (ok, failed_mask of SRS_*).  Raises ZkmiError (BAD_ARG) for a transcript of another context or one
+        that was not loaded under CHECK_SUBGROUP."""
+        assert seed is None or len(seed) == 32
+        failed = C.c_uint32(0)
+        rc = self.lib.zkmi_srs_verify(self.h, srs.h, _buf(seed) if seed is not None else None, C.byref(failed))
+        return self._verdict(rc, failed)
+
+    def pk_verify_contribution(self, before, after, seed=None):
+        """zkmi_pk_verify_contribution: `after` is `before` with one phase-2 contribution applied -> (ok, failed_mask of PK2_*).
+        Raises ZkmiError (BAD_ARG) for keys of different shape or of another context."""
+        assert seed is None or len(seed) == 32
+        failed = C.c_uint32(0)
+        rc = self.lib.zkmi_pk_verify_contribution(self.h, before.h, after.h, _buf(seed) if seed is not None else None, C.byref(failed))
+        return self._verdict(rc, failed)
+
+    def points_adjacent_sums_dev(self, group, d_points, m, seed, dom):
+        """zkmi_g{1,2}_points_adjacent_sums_dev: m subgroup points at device address d_points (affine wire form) ->
+        (lo, hi) = (sum w_i P[i], sum w_i P[i + 1]) over i < m - 1, wire bytes."""
+        w = 96 if group == 1 else 192
+        lo, hi = (C.c_uint8 * w)(), (C.c_uint8 * w)()
+        fn = self.lib.zkmi_g1_points_adjacent_sums_dev if group == 1 else self.lib.zkmi_g2_points_adjacent_sums_dev
+        self._chk(fn(self.h, C.c_void_p(d_points) if d_points else None, C.c_uint64(m), _buf(seed) if seed is not None else None,
+                     C.c_uint32(dom), lo, hi))
+        return bytes(lo), bytes(hi)
+
+    def ceremony_phases(self):
+        """Testing library: ms of the last srs_verify / pk_verify_contribution made through it (weights, conversion, MSMs,
+        pairing products)."""
+        out = (C.c_double * 4)()
+        self._chk(self.z.tlib.zkmi_ceremony_phases(out))
+        return tuple(out)
+
     def groth16_setup_from_srs(self, r1cs, srs, vk_cap=None):
         """zkmi_groth16_setup_from_srs: the relation's key from a phase-1 transcript, gamma = delta = 1 -> (ProvingKey, vk)."""
         cap = 672 + 96 * r1cs.n_pub if vk_cap is None else vk_cap
@@ -1225,6 +1277,10 @@ class Srs:
         self.ctx._chk(self.ctx.lib.zkmi_srs_read(self.ctx.h, self.h, C.c_int32(section), C.c_uint64(first), C.c_uint64(count), out))
         return bytes(out)[: w * count]
 
+    def verify(self, seed=None):
+        """zkmi_srs_verify -> (ok, failed_mask)."""
+        return self.ctx.srs_verify(self, seed)
+
     def free(self):
         if self.h:
             self.ctx.lib.zkmi_srs_free(self.h)
@@ -1258,6 +1314,10 @@ class ProvingKey:
         d1, d2 = (C.c_uint8 * 96)(), (C.c_uint8 * 192)()
         self.ctx._chk(self.ctx.lib.zkmi_pk_contribute(self.ctx.h, self.h, _buf(d), d1, d2))
         return bytes(d1), bytes(d2)
+
+    def verify_contribution(self, before, seed=None):
+        """zkmi_pk_verify_contribution of this key against its predecessor `before` -> (ok, failed_mask)."""
+        return self.ctx.pk_verify_contribution(before, self, seed)
 
     def export_g1_elems(self):
         """zkmi_pk_export_g1_elems: (beta_g1, delta_g1)."""

@@ -36,6 +36,7 @@
 #include "points.hpp"
 #include "points_ntt.hpp"
 #include "setup_srs.hpp"
+#include "ceremony.hpp"
 #include "witness_bound.hpp"
 
 namespace zkmi {
@@ -830,6 +831,24 @@ int32_t zkmi_pk_contribute(zkmi_ctx* ctx, zkmi_pk* pk, const uint8_t d[32], uint
   g1_to_wire(pk->delta_g1, out_delta_g1);
   g2_to_wire(pk->delta_g2, out_delta_g2);
   return ZKMI_OK;
+}
+
+static PkCeremonyView ceremony_view(const zkmi_pk* pk) {
+  return {pk->n_vars, pk->n_pub, pk->log_n, pk->a_query, pk->b_g1_query, pk->b_g2_query, pk->h28, pk->l28,
+          pk->alpha_g1, pk->beta_g1, pk->delta_g1, pk->beta_g2, pk->delta_g2};
+}
+
+int32_t zkmi_pk_verify_contribution(zkmi_ctx* ctx, const zkmi_pk* before, const zkmi_pk* after, const uint8_t seed[32],
+                                    uint32_t* out_failed) {
+  ZK_ENTER(ctx);
+  if (!before || !after || !out_failed) return ZKMI_ERR_BAD_ARG;
+  *out_failed = 0;
+  if (before->ctx != ctx || before->device != ctx->device || after->ctx != ctx || after->device != ctx->device)
+    return ctx->fail(ZKMI_ERR_BAD_ARG, "key of another context");
+  if (before->n_vars != after->n_vars || before->n_pub != after->n_pub || before->log_n != after->log_n)
+    return ctx->fail(ZKMI_ERR_BAD_ARG, "keys of different shape");
+  ZK_HIP(ctx, ctx->drain());  // the keys are idle: nothing queued earlier still writes their arrays
+  return pk_verify_contribution(ctx, ceremony_view(before), ceremony_view(after), seed, out_failed);
 }
 
 int32_t zkmi_pk_load(zkmi_ctx* ctx, const zkmi_r1cs* r, const uint8_t alpha_g1[96], const uint8_t beta_g1[96],

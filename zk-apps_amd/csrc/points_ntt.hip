@@ -213,6 +213,7 @@ int32_t zkmi_srs_load(zkmi_ctx* ctx, int32_t encoding, int32_t checks, const uin
   s->ctx = ctx;
   s->device = ctx->device;
   s->n_tau_g1 = n_tau_g1, s->n_tau_g2 = n_tau_g2, s->n_ab = n_ab;
+  s->checks = checks;  // with the implied bits (point_args_ok)
   void* d_beta = nullptr;
   int32_t rc = srs_section(ctx, 0, 1, tau_g1, n_tau_g1, encoding, checks, reinterpret_cast<void**>(&s->tau_g1), out_where);
   if (rc == ZKMI_OK) rc = srs_section(ctx, 1, 2, tau_g2, n_tau_g2, encoding, checks, reinterpret_cast<void**>(&s->tau_g2), out_where);
@@ -258,6 +259,7 @@ int32_t zkmi_srs_generate(zkmi_ctx* ctx, const uint8_t toxic[96], uint32_t log_n
   s->ctx = ctx;
   s->device = ctx->device;
   s->n_tau_g1 = n1, s->n_tau_g2 = N, s->n_ab = N;
+  s->checks = ZKMI_CHECK_CURVE | ZKMI_CHECK_SUBGROUP;  // multiples of the generators
   std::vector<Fr> p(n1), pa(N), pb(N);
   Fr run = Fr::one();
   for (uint64_t i = 0; i < n1; i++) {

@@ -12,6 +12,7 @@ struct zkmi_srs {
   zkmi::G2Affine* tau_g2 = nullptr;
   zkmi::G2Affine beta_g2;
   uint64_t n_tau_g1 = 0, n_tau_g2 = 0, n_ab = 0;
+  int32_t checks = 0;  // ZKMI_CHECK_* every point was read under (zkmi_srs_generate: all of them); zkmi_srs_verify asks for SUBGROUP
   ~zkmi_srs() {
     if (device >= 0) (void)hipSetDevice(device);
     for (void* p : {(void*)tau_g1, (void*)alpha_tau_g1, (void*)beta_tau_g1, (void*)tau_g2})

@@ -159,6 +159,20 @@ int32_t zkmi_selftest_witness_map_stages(zkmi_ctx* ctx, const zkmi_pk* pk, const
  * bases run the shared-bucket schedule, others the windowed one).  Scalars in HBM. */
 int32_t zkmi_selftest_msm_g1_sum2_dev(zkmi_ctx* ctx, const void* d_scalars_a, const void* d_scalars_b, uint64_t n,
                                       const zkmi_bases_g1* bases, uint8_t out_affine[96]);
+/* The launch schedule MsmEngine::run_device_multi decides in front of its launches (csrc/msm.hpp MsmRunSchedule, csrc/msm_impl.hpp
+ * msm_run_schedule), without a context or a device: the plan of n terms (shared != 0: the shared-bucket plan of prepared
+ * bases; plan_n != 0: n terms under the window width of the plan of plan_n terms, as zkmi_msm_g1_windows_dev sorts them),
+ * engine 0 G1 / 1 G2 / 2 BN254 G1, host_spin (one MSM or one proof by itself), nm MSMs in the call, the MSM_RUN_* flags.
+ * out[37], in this order:
+ *   nwin, c, tot_b, segs_per_win, tot_segs, seg, seg_bits, njobs, plain_job, t_job,
+ *   level2, segs2, tot_segs2, wide, quad_seg, quad_tree, quad_redo, quad_heavy,
+ *   nchunk, nq, tree_block, tree_lds, final_block, final_lds,
+ *   accum (0 G1 single, 1 G1 fused, 2 G1 split2, 3 G2, 4 G2 split2), fused, heavy_nc, partials_per_msm(plan),
+ *   and the constants its bounds come from: lanes per point, segments a sliced tree-sum workgroup takes at once, points per wave
+ *   of the quad / octet kernels, SLOT_PTS, MSM_STAGE_PTS_1, MSM_STAGE_PTS, MSM_TREE_T, MSM_SEG2_MIN_SEGS, MSM_SEG2_LOG.
+ * n_out != 37: ZKMI_ERR_BAD_ARG. */
+int32_t zkmi_selftest_msm_run_schedule(uint64_t n, int32_t shared, uint64_t plan_n, int32_t engine, int32_t host_spin, int32_t nm,
+                                       int32_t flags, int32_t* out, uint32_t n_out);
 /* The column sums of zkmi_groth16_setup_from_srs without a device: csrc/colsum_plan.hpp, csrc/setup_srs.hip.
  * which numbers the query as zkmi_pk_export_query does: 0 a, 1 b_g1, 2 b_g2, 4 l (all n_vars slots; the first n_pub of l
  * are gamma_abc_g1).

@@ -275,6 +275,101 @@ def test_msm_plans_are_consistent(zk):
     assert zk.lib.zkmi_msm_plan_query(C.c_uint64(0), C.c_int32(0), out) != 0
 
 
+RUN_SCHEDULE_FIELDS = (
+    "nwin c tot_b segs_per_win tot_segs seg seg_bits njobs plain_job t_job level2 segs2 tot_segs2 wide quad_seg quad_tree "
+    "quad_redo quad_heavy nchunk nq tree_block tree_lds final_block final_lds accum fused heavy_nc partials_per_msm "
+    "lanes slice_segs quad_per_wave SLOT_PTS STAGE_PTS_1 STAGE_PTS TREE_T SEG2_MIN_SEGS SEG2_LOG").split()
+
+
+def _msm_hpp_enum(name, prefix):
+    """{enumerator without `prefix`: value} of `enum name { A = 0, ... };` as csrc/msm.hpp writes it (every value explicit)."""
+    src = open(os.path.join(ROOT, "zk-apps_amd", "csrc", "msm.hpp")).read()
+    body = re.search(r"\benum %s \{([^}]*)\};" % name, src).group(1)
+    return {k[len(prefix):]: int(v) for k, v in re.findall(r"\b(%s\w+) = (\d+)" % prefix, body)}
+
+
+_FORMS, _KINDS = _msm_hpp_enum("MsmAccumForm", "MSM_ACCUM_"), _msm_hpp_enum("MsmEngineKind", "MSM_ENGINE_")
+ACCUM_G1, ACCUM_G1_MULTI, ACCUM_G1_SPLIT2, ACCUM_G2, ACCUM_G2_SPLIT2 = (_FORMS[k] for k in ("G1", "G1_MULTI", "G1_SPLIT2", "G2", "G2_SPLIT2"))
+ENGINE_G1, ENGINE_G2, ENGINE_BN254 = (_KINDS[k] for k in ("G1", "G2", "BN254"))
+assert len(_FORMS) == 5 and len(_KINDS) == 3
+
+
+def run_schedule(zk, n, shared, engine, host_spin, nm, plan_n=0, flags=0):
+    import types
+
+    out = (C.c_int32 * len(RUN_SCHEDULE_FIELDS))()
+    rc = zk.tlib.zkmi_selftest_msm_run_schedule(C.c_uint64(n), C.c_int32(shared), C.c_uint64(plan_n), C.c_int32(engine),
+                                                C.c_int32(host_spin), C.c_int32(nm), C.c_int32(flags), out, C.c_uint32(len(out)))
+    assert rc == 0, (rc, n, shared, engine, host_spin, nm, plan_n)
+    return types.SimpleNamespace(**dict(zip(RUN_SCHEDULE_FIELDS, out)))
+
+
+def test_msm_run_schedules_fit_their_buffers_and_kernels(zk):
+    """The launch schedule MsmEngine::run_device_multi decides up front (csrc/msm_impl.hpp msm_run_schedule), read through the
+    testing library without a GPU, for every engine, both callers (one MSM or proof by itself / the batch pipeline), windowed
+    and shared-bucket plans, one and four MSMs per call, n = 2^5 .. 2^26 and the 2^24 plan over a small n.  The bounds are
+    those of the buffers (MsmEngine::reserve: SLOT_PTS partials per slot, MSM_STAGE_PTS staged slices of which the one-lane
+    tree sums use the first MSM_STAGE_PTS_1) and of the kernels (treesum_final_body: one point per slice in ONE workgroup of
+    at most MSM_TREE_T points; treesum_body: a slice workgroup takes slice_segs segments at once; k_segreduce2: 16 segment
+    sums per super-segment; TreeLevel2 is a parameter of the one-lane / lane-pair tree sums only), all exported by the hook.
+    The quad / octet final sum strides over its slices a wave at a time (msm_quad.hpp k_treesum_final_q), so its slices are
+    held to the stage and to "none empty", not to a workgroup's points."""
+    pow2 = lambda v: v > 0 and v & (v - 1) == 0
+    cases = [(1 << k, shared, 0) for k in range(5, 27) for shared in (0, 1)] + [((1 << 12) - 3, 0, 1 << 24)]
+    seen = set()
+    for n, shared, plan_n in cases:
+        for engine in (ENGINE_G1, ENGINE_G2, ENGINE_BN254):
+            for host_spin in (0, 1):
+                for nm in (1, 4):
+                    s = run_schedule(zk, n, shared, engine, host_spin, nm, plan_n)
+                    what = (n, shared, plan_n, engine, host_spin, nm, vars(s))
+                    lists = s.njobs * s.nwin
+                    assert s.lanes == (2 if engine == ENGINE_G2 else 1)
+                    assert lists <= s.SLOT_PTS and (2 + s.seg_bits) * s.nwin <= s.SLOT_PTS, what
+                    assert s.njobs * s.nwin == s.partials_per_msm, what
+                    assert s.segs_per_win == 1 << s.seg_bits and s.tot_segs == s.nwin * s.segs_per_win, what
+                    # one-lane / lane-pair slices
+                    assert pow2(s.nchunk) and s.nchunk <= s.TREE_T and lists * s.nchunk <= s.STAGE_PTS_1, what
+                    assert s.final_block // s.lanes >= s.nchunk and s.final_block <= s.lanes * s.TREE_T, what
+                    assert s.nchunk == 1 or s.nchunk * s.slice_segs <= s.segs_per_win, what
+                    assert s.tree_block <= s.lanes * s.TREE_T and s.tree_block % 64 == 0 and s.final_block % 64 == 0, what
+                    # quad / octet slices
+                    assert pow2(s.nq) and lists * s.nq <= s.STAGE_PTS, what
+                    assert s.nq == 1 or s.nq * s.quad_per_wave <= s.segs_per_win, what
+                    # second level
+                    if s.level2:
+                        assert shared and s.segs_per_win >= s.SEG2_MIN_SEGS and s.segs_per_win % 16 == 0, what
+                        assert not s.quad_seg and not s.quad_tree, what
+                        assert s.segs2 << s.SEG2_LOG == s.segs_per_win and s.tot_segs2 == s.nwin * s.segs2, what
+                        assert s.t_job == s.njobs - 2 and s.plain_job == s.njobs - 1, what
+                    else:
+                        assert s.t_job == -1 and s.plain_job == (s.njobs - 1 if shared else -1), what
+                    assert s.wide == (not shared and s.c > 16), what
+                    if s.wide:
+                        assert not s.quad_seg and not s.quad_tree, what
+                    # what the documents say in words (DESIGN.md 4.1, 4.4)
+                    if not s.wide:  # one MSM by itself takes all four quad stages, the batch pipeline only redo and heavy
+                        assert (s.quad_seg, s.quad_tree, s.quad_redo, s.quad_heavy) == ((1, 1, 1, 1) if host_spin else (0, 0, 1, 1)), what
+                    if engine == ENGINE_G2:
+                        assert s.accum == (ACCUM_G2_SPLIT2 if host_spin and s.tot_b <= 1 << 15 else ACCUM_G2) and not s.fused, what
+                    else:
+                        assert s.fused == (nm > 1), what
+                        assert s.accum == ((ACCUM_G1_SPLIT2 if s.tot_b <= 1 << 16 else ACCUM_G1_MULTI) if nm > 1 else ACCUM_G1), what
+                    seen.add((s.accum, bool(s.level2), s.nchunk > 1, s.nq > 1, bool(s.wide)))
+    assert {a for a, *_ in seen} == {ACCUM_G1, ACCUM_G1_MULTI, ACCUM_G1_SPLIT2, ACCUM_G2, ACCUM_G2_SPLIT2}
+    assert any(l2 for _, l2, *_ in seen) and any(w for *_, w in seen)
+    # the 13-window, 20-bit plan: two-wave segment sums (no quad form) and 16 tree slices (13 windows x 16 jobs x 16 <= 4096)
+    for n, plan_n in ((1 << 24, 0), ((1 << 12) - 3, 1 << 24)):
+        s = run_schedule(zk, n, 0, ENGINE_G1, 1, 1, plan_n)
+        assert (s.c, s.nwin, s.wide, s.quad_seg, s.quad_tree, s.nchunk) == (20, 13, 1, 0, 0, 16), vars(s)
+        assert s.quad_redo and not s.heavy_nc and not s.quad_heavy  # (the partitioned windows' heavy lists stay with the complete-law kernel)
+    for bad in ((0, 0, 0, 0, 1, 1), (1 << 12, 0, 0, 3, 1, 1), (1 << 12, 0, 0, 0, 1, 5), (1 << 12, 1, 1 << 24, 0, 1, 1)):
+        n, shared, plan_n, engine, host_spin, nm = bad
+        out = (C.c_int32 * len(RUN_SCHEDULE_FIELDS))()
+        assert zk.tlib.zkmi_selftest_msm_run_schedule(C.c_uint64(n), C.c_int32(shared), C.c_uint64(plan_n), C.c_int32(engine),
+                                                      C.c_int32(host_spin), C.c_int32(nm), C.c_int32(0), out, C.c_uint32(len(out))) != 0
+
+
 def test_assembly_scalar_multiplications_selftest(zk):
     """Host arithmetic of proof assembly: fixed-base delta tables and the joint s*A + r*B1 multiplication equal
     plain double-and-add in G1 and G2 (scalars 0, 1, r - 1 and random; P + P and P - P in the joint form)."""

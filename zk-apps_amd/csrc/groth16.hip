@@ -1197,7 +1197,7 @@ static int32_t prove_enqueue_z(zkmi_ctx* ctx, const zkmi_pk* pk, const void* con
   const int s0 = 4 * par, g2s = par;
   // ZKMI_HEAVY_ON=1 (A/B library): heavy-bucket kernels on their own side stream (round 2; created on first use); default:
   // at the head of each MSM's reduction stream, 0: in line on the accumulation streams (msm_impl.hpp run_device)
-  const bool heavy_side = ZK_TUNE("ZKMI_HEAVY_ON", 2) == 1;
+  const bool heavy_side = msm_tune_heavy_on() == 1;
   if (heavy_side) ZK_HIP(ctx, ctx->lazy_stream(&ctx->stream_heavy, false));
   const hipStream_t sth = heavy_side ? ctx->stream_heavy : nullptr;
   // MSMs over the assignment z[1..): one digit sort, four bucket passes.  Every
@@ -1284,7 +1284,7 @@ static int32_t prove_enqueue_z(zkmi_ctx* ctx, const zkmi_pk* pk, const void* con
   const int lh_mode = ZK_TUNE("ZKMI_LH_MERGE", 2);
   const uint32_t N = 1u << pk->log_n;
   const bool same_set = sh && same_bucket_set(sz.plan, G > 1 ? msm_make_plan_shared_batch(N, G) : msm_make_plan_shared(N));
-  const bool nocall_g1 = ZK_TUNE("ZKMI_ACCUM", 3) == 2 || ZK_TUNE("ZKMI_ACCUM", 3) == 3;
+  const bool nocall_g1 = msm_tune_accum() == 2 || msm_tune_accum() == 3;
   // Not for ONE proof by itself (zkmi_groth16_prove[_dev]): there the merged reduction is the tail of the proof -- three
   // additions per bucket instead of two after the last accumulation, where L's own reduction used to run beside the H
   // accumulation -- and its latency went from 18.9 to 20.1 ms at 2^20 for nothing (lh_merge_modes_ab.txt).
@@ -1349,7 +1349,7 @@ static int32_t prove_enqueue_h(zkmi_ctx* ctx, const zkmi_pk* pk, uint32_t G, int
   if (spread) ZK_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_sorth[par], 0));  // the sort of h, queued on the front stream
   PhaseTimer* t = ctx->timer();
   const bool sh = pk->shared;
-  const bool heavy_side = ZK_TUNE("ZKMI_HEAVY_ON", 2) == 1;
+  const bool heavy_side = msm_tune_heavy_on() == 1;
   if (heavy_side) ZK_HIP(ctx, ctx->lazy_stream(&ctx->stream_heavy, false));
   const hipStream_t sth = heavy_side ? ctx->stream_heavy : nullptr;
   const bool sort_side = prover_sort_side();

@@ -139,6 +139,51 @@ template <> struct HostFieldOf<BnFq28> { using type = BnFq; };
 // MsmEngine::run_device flags (msm_impl.hpp run_device_multi); MSM_RUN_TWO_WAVES: the G1 accumulation capped at two waves per SIMD
 enum { MSM_RUN_NO_REDUCE = 1, MSM_RUN_ADD_AT_REDUCE = 2, MSM_RUN_TWO_WAVES = 4 };
 
+// The two engine switches that callers of the engine read too (groth16.hip), default written here only.
+// ZKMI_HEAVY_ON: where the heavy-bucket kernels run: 2 = at the head of the reduction's stream (the product), 1 = on the side
+// stream `st_heavy` (round 2), 0 = in line on the accumulation stream.  ZKMI_ACCUM: generation of the G1 accumulation
+// kernels: 3 = call-free at three waves per SIMD (the product), 2 = at two, 0 | 1 = the retired ones (msm_impl_exp.hpp).
+inline int msm_tune_heavy_on() { return ZK_TUNE("ZKMI_HEAVY_ON", 2); }
+inline int msm_tune_accum() { return ZK_TUNE("ZKMI_ACCUM", 3); }
+
+enum MsmEngineKind { MSM_ENGINE_G1 = 0, MSM_ENGINE_G2 = 1, MSM_ENGINE_BN254 = 2 };
+// the product's five accumulation launches; what else the A/B library launches: msm_impl_exp.hpp
+enum MsmAccumForm { MSM_ACCUM_G1 = 0, MSM_ACCUM_G1_MULTI = 1, MSM_ACCUM_G1_SPLIT2 = 2, MSM_ACCUM_G2 = 3, MSM_ACCUM_G2_SPLIT2 = 4 };
+
+// Everything MsmEngine::run_device_multi decides about its launches, decided once in front of them by msm_run_schedule
+// (msm_impl.hpp): pure arithmetic on the common plan, the engine and the call's flags -- no HIP call, no engine state, so a
+// test can read it without a GPU (zkmi_selftest_msm_run_schedule).
+struct MsmRunSchedule {
+  // buckets of one MSM; segments (of `seg` buckets, seg_bits = log2 segs_per_win) per window or partition, and over all
+  uint32_t tot_b, segs_per_win, tot_segs;
+  int seg, seg_bits;
+  // partial sums per window: [0] plain sum of segw, the bit jobs, plain_job (shared plans: plain sum of segsum, else -1),
+  // t_job (second level: plain sum of segt2, else -1); msm_njobs
+  int njobs, plain_job, t_job;
+  // second running-sum level (k_segreduce2): one-lane / lane-pair reductions of shared plans with long segment lists;
+  // seg2_log = MSM_SEG2_LOG or 0: what slot_plan[slot].seg2_log becomes
+  bool level2;
+  int seg2_log;
+  uint32_t segs2, tot_segs2;
+  // wide: partitioned big windows (windowed plan, c > 16).  quad_*: the quad (G1) / octet (G2) form of the segment sums,
+  // tree sums, redo pass and summing of heavy-bucket partials, "this plan allows it" included
+  bool wide, quad_seg, quad_tree, quad_redo, quad_heavy;
+  // tree sums: slices per job list of the one-lane / lane-pair kernels (nchunk) and of the quad kernels (nq), 1 = unsliced;
+  // threads and dynamic LDS bytes of k_treesum / k_treesum_final
+  uint32_t nchunk, nq, tree_block, tree_lds, final_block, final_lds;
+  // the accumulation: which launch; fused = one for all MSMs of the call; nocall = it leaves a redo list (the call-free
+  // kernels: always, in the product)
+  MsmAccumForm accum;
+  bool fused, nocall;
+  // heavy buckets: msm_tune_heavy_on(); heavy_nc = the call-free kernels add the points, the complete-law kernel only the
+  // partial sums; heavy_deferred = kernels of another stream queued BEHIND the accumulation launch (A/B: ZKMI_HEAVY_DEFER)
+  int heavy_on;
+  bool heavy_nc, heavy_deferred;
+  // A/B library only (msm_impl_exp.hpp); the product's values select nothing
+  int exp_accum_mode, exp_accum_block, exp_accum_rounds, exp_mask_bits;
+  bool exp_accum_q, exp_two_waves, exp_g2_tree_unsplit;
+};
+
 template <class F>
 struct MsmEngine {
   using HF = typename HostFieldOf<F>::type;
@@ -194,13 +239,18 @@ struct MsmEngine {
   // (which own buckets the accumulation skips) run on `st_heavy` beside the accumulation when given:
   // with uniform scalars their list is empty, and on `st` the empty launches waited ~0.8 ms each for
   // a free workgroup slot before the next accumulation could start
-  // bucket_slot >= 0 and != slot: add INTO the bucket array of that slot (filled by an earlier run with MSM_RUN_NO_REDUCE)
-  // and reduce the sum of both MSMs; see run_device_multi in msm_impl.hpp
+  // Two MSMs whose results are only ever added share one reduction: the first runs with MSM_RUN_NO_REDUCE, the second
+  // names the first one's slot in bucket_slot (!= slot) and
+  //   with MSM_RUN_ADD_AT_REDUCE (the product): accumulates into its own array, and its segment sums add both arrays
+  //     (bucket_slot3 >= 0: a third one too);
+  //   without the flag (an A/B variant, libzkmi_exp.so only; the product refuses it): its kernels add INTO that slot's array.
+  // See run_device_multi in msm_impl.hpp.
   hipError_t run_device(const MsmSort& sort, const Affine<F>* d_bases, hipStream_t st, hipStream_t st_reduce,
                         PhaseTimer* prof, int ph_accum, int ph_reduce, int slot = 0, hipStream_t st_heavy = nullptr,
                         int bucket_slot = -1, int flags = 0, int bucket_slot3 = -1);
   // nm <= 4 MSMs of one plan shape (sorts[m] may repeat: several tables over one sort), each with its own slot and
-  // reduction stream; the G1 call-free kernels accumulate them in one launch (one small proof: A, B1, L and H side by side)
+  // reduction stream; the G1 call-free kernels accumulate them in one launch (one small proof: A, B1, L and H side by side).
+  // The launches are decided up front (MsmRunSchedule) and queued in stages; every refusal comes before the first of them.
   hipError_t run_device_multi(const MsmSort* const* sorts, const Affine<F>* const* d_bases, int nm, hipStream_t st,
                               const hipStream_t* st_reduces, PhaseTimer* prof, int ph_accum, int ph_reduce, const int* slots,
                               hipStream_t st_heavy = nullptr, const int* bucket_slots = nullptr, int flags = 0, int third_slot = -1);

@@ -522,18 +522,6 @@ __global__ void __launch_bounds__(64 * BW, W)
 k_accum_g1_nc(const AccumArgs<F, MULTI> args, uint32_t total_buckets) {
   accum_g1_nc_body<F, BW, MULTI, INTO>(args, total_buckets);
 }
-#ifdef ZKMI_EXPERIMENTS
-}  // namespace zkmi
-#include "msm_impl_exp.hpp"  // retired kernel generations: A/B library only
-namespace zkmi {
-// TIMING ONLY (ZKMI_GATHER_MASK_BITS = k > 0): every table index of a sort is cut to its low k bits before the accumulation
-// reads it, so that all gathers hit a sub-table of 2^k entries that stays in L2.  The sums are WRONG by design: what is left
-// of a launch's time and held clock is the arithmetic alone, the bound of what any change to the fetch path can give.
-template <int UNUSED = 0>
-__global__ void k_mask_sorted(uint32_t* __restrict__ sorted, uint64_t n, uint32_t keep) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) sorted[i] &= keep;
-}
-#endif
 // acc += o for acc, o != O; false when the sum needs the complete group law (o = +-acc): same contract as madd_generic
 template <class F>
 __device__ __forceinline__ bool add_generic(XYZZ<F>& a, const XYZZ<F>& o) {
@@ -1472,6 +1460,393 @@ static inline int msm_njobs(const MsmPlan& pl) {
   return 1 + msm_seg_bits(pl) + (pl.shared ? 1 : 0);
 }
 
+// points a wave of the quad (G1, BN254 G1) / octet (G2) kernels holds
+static inline uint32_t msm_quad_per_wave(MsmEngineKind kind) {
+  return kind == MSM_ENGINE_G2 ? XYZZQ<Fq28, 0, true>::PER_WAVE : XYZZQ<Fq28, 0, false>::PER_WAVE;
+}
+
+// The launch schedule of one run_device_multi call (msm.hpp MsmRunSchedule), from the plan all its MSMs share, the engine,
+// MsmEngine::host_spin (ONE MSM or ONE proof by itself: the latency path; false: the batch prover's pipeline), the number
+// of MSMs, the MSM_RUN_* flags, and whether an MSM adds INTO another one's bucket array (A/B library).
+inline MsmRunSchedule msm_run_schedule(const MsmPlan& pl, MsmEngineKind kind, bool host_spin, int nm, int flags, bool any_into) {
+  // Every tuning switch of the engine, read here and nowhere else; the product compiles each to its default (tune.hpp).
+  //   ZKMI_ACCUM (msm.hpp) / ZKMI_ACCUM_G2 = 0 | 1: the retired accumulation generations (madd with an out-of-line doubling
+  //     path; ZKMI_ACCUM_BLOCK = 64 | 256 threads per workgroup, ZKMI_ACCUM_ROUNDS = R load-ordered bucket groups per wave),
+  //     2 | 3: the call-free kernels at 2 / 3 waves per SIMD (the product: 3 for G1, 2 for G2)
+  //   ZKMI_QUAD / ZKMI_QUAD_BATCH (G2, the octet form: ZKMI_QUAD_G2 / ZKMI_QUAD_G2_BATCH): the reduction-side kernels with every
+  //     complete addition split over a lane quad (msm_quad.hpp): bit 0 = segment sums, 1 = tree sums, 2 = redo pass, 3 = the
+  //     summing of heavy-bucket partials, 4 = (A/B) the accumulation itself.  One-wave workgroups at the accumulation
+  //     kernels' register count, placed beside them.  The latency path takes all four: a chain of 4 products per dependent
+  //     addition instead of 14; the pipeline only redo and heavy: the quad form issues 1.37 x the instructions
+  //   ZKMI_HEAVY_ON (msm.hpp), ZKMI_HEAVY_NC = 0: the complete-law heavy kernel of rounds 1-4 for everything, ZKMI_HEAVY_DEFER
+  //     = 1: round 6, no gain (g2_split2_ab.txt)
+  //   ZKMI_FORCE_MULTI = 1: a lone MSM through the fused launch too (so that the generic entry points, with their degenerate
+  //     inputs, reach k_accum_g1_split2 and the MULTI kernel form)
+  //   ZKMI_SOLO_SPLIT / ZKMI_SOLO_SPLIT_G2 = 0: one lane (pair) per bucket for small plans too
+  //   ZKMI_ACCUM_W2 = 1: every lone G1 accumulation capped at two waves (12 % slower)
+  //   ZKMI_G2_TREE_SPLIT = 0: the unsplit G2 tree sum;  ZKMI_GATHER_MASK_BITS: TIMING ONLY, see k_mask_sorted
+  MsmRunSchedule s = {};
+  const bool g2 = kind == MSM_ENGINE_G2;
+  s.exp_accum_mode = g2 ? ZK_TUNE("ZKMI_ACCUM_G2", 2) : msm_tune_accum();
+  const int quad_mask = g2 ? (host_spin ? ZK_TUNE("ZKMI_QUAD_G2", 15) : ZK_TUNE("ZKMI_QUAD_G2_BATCH", 12))
+                           : (host_spin ? ZK_TUNE("ZKMI_QUAD", 15) : ZK_TUNE("ZKMI_QUAD_BATCH", 12));
+  s.exp_accum_block = ZK_TUNE("ZKMI_ACCUM_BLOCK", 64) == 256 ? 256 : 64;
+  s.exp_accum_rounds = ZK_TUNE("ZKMI_ACCUM_ROUNDS", 0);
+  s.exp_mask_bits = ZK_TUNE("ZKMI_GATHER_MASK_BITS", 0);
+  s.exp_two_waves = (flags & MSM_RUN_TWO_WAVES) || ZK_TUNE("ZKMI_ACCUM_W2", 0) == 1;
+  s.exp_g2_tree_unsplit = ZK_TUNE("ZKMI_G2_TREE_SPLIT", 1) == 0;
+  s.heavy_on = msm_tune_heavy_on();
+  const bool t_heavy_nc = ZK_TUNE("ZKMI_HEAVY_NC", 1) != 0, t_heavy_defer = ZK_TUNE("ZKMI_HEAVY_DEFER", 0) != 0;
+  const bool t_solo_split = ZK_TUNE("ZKMI_SOLO_SPLIT", 1) != 0, t_solo_split_g2 = ZK_TUNE("ZKMI_SOLO_SPLIT_G2", 1) != 0;
+  const bool t_force_multi = ZK_TUNE("ZKMI_FORCE_MULTI", 0) != 0;
+
+  const uint32_t lanes = g2 ? 2 : 1;  // lanes per point of the one-lane / lane-pair kernels
+  const uint32_t point_bytes = g2 ? sizeof(XYZZ<Fq2_28>) : kind == MSM_ENGINE_BN254 ? sizeof(XYZZ<BnFq28>) : sizeof(XYZZ<Fq28>);
+  s.nocall = s.exp_accum_mode == 2 || s.exp_accum_mode == 3;
+  s.tot_b = pl.nwin * pl.nb;
+  s.segs_per_win = pl.nb >> pl.seg_log;
+  s.tot_segs = pl.nwin * s.segs_per_win;
+  s.seg = 1 << pl.seg_log;
+  s.seg_bits = msm_seg_bits(pl);
+  // the partitioned big windows keep the one-lane segment and tree sums: their reduction has the chip to itself
+  s.wide = !pl.shared && pl.c > 16;
+  s.quad_seg = (quad_mask & 1) && !s.wide;
+  s.quad_tree = (quad_mask & 2) && !s.wide;
+  s.quad_redo = (quad_mask & 4) != 0;
+  // the quad / octet kernels, the windowed plans and their exchange layouts keep the single level
+  s.level2 = pl.shared && !s.quad_seg && !s.quad_tree && s.segs_per_win >= MSM_SEG2_MIN_SEGS;
+  s.seg2_log = s.level2 ? MSM_SEG2_LOG : 0;
+  s.segs2 = s.segs_per_win >> MSM_SEG2_LOG;
+  s.tot_segs2 = s.tot_segs >> MSM_SEG2_LOG;
+  MsmPlan reduced = pl;
+  reduced.seg2_log = s.seg2_log;
+  s.njobs = msm_njobs(reduced);
+  s.plain_job = pl.shared ? s.njobs - 1 : -1;
+  s.t_job = s.level2 ? s.njobs - 2 : -1;
+
+  // One small G2 MSM by itself (the G2 launch of a single small proof): two lane pairs per bucket halve the chain (2^13 1.99
+  // -> 1.74 ms, 2^14 1.92 -> 1.77, 2^15 2.38 -> 2.2; at 2^16 buckets the chip is full and it costs 0.08 ms:
+  // profiles/r06/experiments/g2_split2_ab.txt).  G1: a fused launch of small plans (one small proof) takes two lanes per bucket.
+  s.fused = !g2 && s.nocall && (nm > 1 || (t_force_multi && !any_into));
+  if (g2) s.accum = host_spin && s.tot_b <= (1u << 15) && t_solo_split_g2 ? MSM_ACCUM_G2_SPLIT2 : MSM_ACCUM_G2;
+  else if (s.fused) s.accum = t_solo_split && s.tot_b <= (1u << 16) ? MSM_ACCUM_G1_SPLIT2 : MSM_ACCUM_G1_MULTI;
+  else s.accum = MSM_ACCUM_G1;
+  s.exp_accum_q = (quad_mask & 16) && s.tot_b <= (1u << 16);  // (G2 and the fused G1 launch, in front of split2)
+
+  // the call-free kernels take the additions of points (DESIGN.md 4.1 "heavy buckets"); not for lists the plan cannot hold
+  // (decided on the device), the partitioned big windows' thousands of entries, or the A/B accumulate-into forms
+  s.heavy_nc = t_heavy_nc && !s.wide && !any_into;
+  s.quad_heavy = (quad_mask & 8) && s.heavy_nc;
+  s.heavy_deferred = host_spin && s.tot_b <= (1u << 16) && (quad_mask & 8) && s.heavy_on == 2 && t_heavy_defer;
+
+  // One-lane / lane-pair tree sums: a workgroup of MSM_TREE_T threads takes two segments per point.  Job lists longer than
+  // that are cut into nchunk slices (k_treesum_final adds them), as many as leave no slice empty, within a cap:
+  //   plans of at most 2^16 buckets: all of them, or none where the stage cannot hold them (fewer, longer slices -- at most
+  //     16, 8 or 4 -- measured the same group rates and single-proof latencies: profiles/r05/experiments/tree_slices_ab.txt);
+  //   one windowed MSM of up to 2^19 buckets: as many as the chip holds at once (1024 workgroups; 16 windows x 13 jobs: 16;
+  //     3 328 workgroups of 9 dependent additions each, in three rounds, took longer than 208 of 23; see plan_set_heavy);
+  //   partitioned big windows: 2^(c-5) segments per list on ONE workgroup are a chain of 2^(c-12) dependent additions (5 ms
+  //     at c = 20); as many as the stage holds (16 at 13 windows x 16 jobs);
+  //   every other plan: unsliced.
+  const uint32_t per_block = 2 * MSM_TREE_T / lanes;
+  const uint64_t lists = (uint64_t)s.njobs * pl.nwin;
+  const uint32_t fit = s.segs_per_win / per_block < MSM_TREE_T ? s.segs_per_win / per_block : MSM_TREE_T;
+  s.nchunk = 1;
+  if (fit > 1 && s.tot_b <= (1u << 16)) {
+    if (lists * fit <= MSM_STAGE_PTS_1) s.nchunk = fit;
+  } else if (fit > 1 && ((!pl.shared && s.tot_b <= (1u << 19)) || s.wide)) {
+    const uint32_t cap = s.tot_b <= (1u << 19) ? 1024 : MSM_STAGE_PTS_1;
+    for (s.nchunk = fit; s.nchunk > 1 && lists * s.nchunk > cap;) s.nchunk >>= 1;
+  }
+  // sliced: MSM_TREE_T / lanes points per workgroup (G2: 64 lane pairs); unsliced: MSM_TREE_T points (G2: 128 pairs -- the
+  // unsplit form's 330-register additions made this the slowest link of a proof's tail)
+  const uint32_t tree_points = s.nchunk > 1 ? MSM_TREE_T / lanes : MSM_TREE_T;
+  s.exp_g2_tree_unsplit = s.exp_g2_tree_unsplit && g2 && s.nchunk == 1;  // (then by the one-lane kernel)
+  s.tree_block = tree_points * (s.exp_g2_tree_unsplit ? 1 : lanes);
+  s.tree_lds = tree_points * point_bytes;
+  // the final sum: a point per slice, at least a wave
+  for (s.final_block = 64; s.final_block < lanes * s.nchunk;) s.final_block <<= 1;
+  s.final_lds = s.final_block / lanes * point_bytes;
+  // Quad / octet tree sums: one wave (16 quads / 8 octets) per slice; as many slices as make the two levels equally deep (a
+  // point walks len / (PER_WAVE slices) segments, the final sum slices / PER_WAVE), within the stage and none empty
+  const uint32_t per_wave = msm_quad_per_wave(kind);
+  for (s.nq = 1; (uint64_t)s.nq * s.nq * 4 <= s.segs_per_win;) s.nq <<= 1;  // ~ sqrt(segs_per_win), rounded to a power of two
+  while (s.nq > 1 && (lists * s.nq > MSM_STAGE_PTS || s.nq * per_wave > s.segs_per_win)) s.nq >>= 1;
+  return s;
+}
+
+// One run_device_multi call: its arguments, and per MSM what the stages below share.
+template <class F>
+struct MsmRunCall {
+  // (the arguments, in their order)
+  const MsmSort* const* sorts;
+  const Affine<F>* const* bases;
+  int nm;
+  hipStream_t st;
+  const hipStream_t* st_reduces;
+  PhaseTimer* prof;
+  int ph_accum, ph_reduce;
+  const int* slots;
+  hipStream_t st_heavy;
+  const int* bucket_slots;
+  int flags, third_slot;
+  bool any_into;
+  // per MSM: the bucket array its kernels write; its slot's redo list ([0] length, [1 ..] list, [cap_buckets + 1] ticket:
+  // k_accum_redo); the stream of its heavy-bucket kernels, and whether that is another one than the accumulation's (then
+  // they are queued in front of it)
+  XYZZ<F>* bk[MSM_MULTI_MAX];
+  uint32_t* redo[MSM_MULTI_MAX];
+  hipStream_t heavy_stream[MSM_MULTI_MAX];
+  bool heavy_first[MSM_MULTI_MAX];
+  // bucket_slots[m] != slots[m] names another MSM's array.  MSM_RUN_ADD_AT_REDUCE (the product): a second SOURCE of this
+  // MSM's reduction (k_segreduce adds both arrays); without the flag (A/B library): the array its kernels add INTO
+  bool add_at_reduce() const { return (flags & MSM_RUN_ADD_AT_REDUCE) != 0; }
+  int bslot(int m) const { return bucket_slots ? bucket_slots[m] : slots[m]; }
+  bool into(int m) const { return !add_at_reduce() && bslot(m) != slots[m]; }
+  bool second(int m) const { return add_at_reduce() && bslot(m) != slots[m]; }
+  SortView view(int m) const { return SortView{sorts[m]->begin, sorts[m]->count, sorts[m]->perm, sorts[m]->sorted, sorts[m]->plan.heavy_thr}; }
+  // the argument block of a fused accumulation launch (slots past nm repeat the first MSM)
+  AccumArgs<F, true> fused_args() const {
+    AccumArgs<F, true> set;
+    for (int m = 0; m < MSM_MULTI_MAX; m++) {
+      const int k = m < nm ? m : 0;
+      set.bases_[m] = bases[k];
+      set.buckets_[m] = bk[k];
+      set.redo_[m] = redo[k];
+      set.sort_[m] = view(k);
+    }
+    return set;
+  }
+};
+
+// What the engine's steps launch: the kernels of its lane layout with LANES lanes per point (msm_impl.hpp "Lane layouts"),
+// the quad / octet point type, and the accumulation's waves per SIMD.  Grid, block and LDS sizes below are expressions in LANES.
+template <class F, int U = 0>
+struct MsmEngineKernels {  // OneLane<F>: G1, BN254 G1
+  static constexpr uint32_t LANES = 1, ACCUM_WAVES = 3;
+  static constexpr MsmEngineKind KIND = std::is_same<F, BnFq28>::value ? MSM_ENGINE_BN254 : MSM_ENGINE_G1;
+  using QPT = XYZZQ<F, 0, false>;
+  static constexpr auto heavy_nc = &k_accum_heavy_nc<F, 3>;
+  static constexpr auto segreduce2 = &k_segreduce2<F>;
+  static constexpr auto treesum = &k_treesum<F>;
+  static constexpr auto treesum_final = &k_treesum_final<F>;
+};
+template <int U>
+struct MsmEngineKernels<Fq2_28, U> {  // LanePair: G2
+  static constexpr uint32_t LANES = 2, ACCUM_WAVES = 2;
+  static constexpr MsmEngineKind KIND = MSM_ENGINE_G2;
+  using QPT = XYZZQ<Fq28, 0, true>;
+  static constexpr auto heavy_nc = &k_accum_heavy_nc_g2<2 + U>;
+  static constexpr auto segreduce2 = &k_segreduce2_g2_split<U>;
+  static constexpr auto treesum = &k_treesum_g2_split<U>;
+  static constexpr auto treesum_final = &k_treesum_final_g2_split<U>;
+};
+
+#ifdef ZKMI_EXPERIMENTS
+}  // namespace zkmi
+#include "msm_impl_exp.hpp"  // A/B library only: the retired kernel generations and what selects them
+namespace zkmi {
+#endif
+
+// ---- stages of run_device_multi, in the order it runs them ----
+
+// Records `ev` on stream `on`; `waiter`, where that is another stream, waits for it; `reads`: the sort whose buffers the
+// kernels in front of `ev` read keeps it for the next sort into them, which may be queued on another stream (MsmSort::readers).
+static inline hipError_t msm_signal(hipEvent_t ev, hipStream_t on, hipStream_t waiter, const MsmSort* reads = nullptr) {
+  hipError_t e = hipEventRecord(ev, on);
+  if (e == hipSuccess && waiter != on) e = hipStreamWaitEvent(waiter, ev, 0);
+  if (e == hipSuccess && reads) reads->readers.push_back(ev);
+  return e;
+}
+
+// The heavy-bucket kernels of one MSM.  Heavy and light buckets are disjoint, so they only have to see the sort complete.
+template <class F>
+static void msm_launch_heavy(const MsmEngine<F>& eng, const MsmRunCall<F>& c, const MsmRunSchedule& s, int m) {
+  using K = MsmEngineKernels<F>;
+  const MsmSort& sort = *c.sorts[m];
+  const hipStream_t hs = c.heavy_stream[m];
+  // MSMs of different slots may overlap: partial sums, plan and tickets per slot
+  XYZZ<F>* const hp = eng.heavy_partial + (size_t)c.slots[m] * ((size_t)MSM_HPOOL + MSM_HNC_POOL);
+  XYZZ<F>* const pool_nc = hp + MSM_HPOOL;
+  uint32_t* const hplan = eng.heavy_plan + (size_t)c.slots[m] * MSM_HPLAN_WORDS;
+  uint32_t* const tk = eng.heavy_ticket + (size_t)c.slots[m] * MSM_HEAVY_CAP;
+  if (s.heavy_nc) {
+    hipLaunchKernelGGL(k_heavy_plan<0>, dim3(1), dim3(64), 0, hs, sort.heavy, sort.count, sort.begin, hplan, 64u / K::LANES, 0u);
+    // one-wave workgroups, grid-strided over the wave-items: twice the chip's wave slots (an empty list costs one placement)
+    hipLaunchKernelGGL(K::heavy_nc, dim3(2048 * K::ACCUM_WAVES), dim3(64), 0, hs, c.bases[m], sort.sorted, hplan, pool_nc);
+  }
+  if (s.quad_heavy) {
+    // both modes of the plan in one-wave workgroups of quads / octets: nothing of 300 registers has to find a SIMD beside the accumulation
+    hipLaunchKernelGGL(k_heavy_q<typename K::QPT>, dim3(1024), dim3(64), 0, hs, c.bases[m], sort.begin, sort.count, sort.heavy,
+                       sort.sorted, c.bk[m], hp, tk, hplan, pool_nc);
+    return;
+  }
+  // the complete-law kernel; partitioned big windows: the tail of the list in a launch of its own (see k_accum_heavy)
+  const uint32_t* const plan_arg = s.heavy_nc ? hplan : nullptr;
+  const size_t lds = sizeof(XYZZ<F>) * MSM_TREE_T / K::LANES;
+  for (int tail = 0; tail <= (s.wide ? 1 : 0); tail++) {
+    const dim3 grid = tail ? dim3(1, 4096) : dim3(MSM_HSPLIT, 8);
+    const uint32_t first = tail ? MSM_HEAVY_CAP : 0u, last = !tail && s.wide ? MSM_HEAVY_CAP : 0xffffffffu;
+    if constexpr (K::LANES == 2)
+      hipLaunchKernelGGL(k_accum_heavy_g2_split<0>, grid, dim3(MSM_TREE_T), lds, hs, c.bases[m], sort.begin, sort.count, sort.heavy,
+                         sort.sorted, c.bk[m], hp, tk, first, last, tail ? nullptr : plan_arg, pool_nc);
+    else
+      hipLaunchKernelGGL(k_accum_heavy<F>, grid, dim3(MSM_TREE_T), lds, hs, c.bases[m], sort.begin, sort.count, sort.heavy,
+                         sort.sorted, c.bk[m], hp, tk, c.into(m) ? 1u : 0u, first, last, tail ? nullptr : plan_arg, pool_nc);
+  }
+}
+
+// In front of the accumulation: where MSM m's heavy-bucket kernels run, and their launch where that is another stream.
+// They run at the head of the REDUCTION's stream.  With uniform scalars the heavy list is empty, but an empty 512-workgroup
+// launch still has to be placed: on a normal-priority stream it queued behind the next accumulation's workgroups (0.9 ms G1 /
+// 9.8 ms G2 average in the round-2 trace) and every reduction waited for it.  The reduction streams have high priority, so
+// there the launch is placed as soon as any workgroup retires, and no cross-stream event sits between it and the
+// reduction.  On another stream they are queued BEFORE the accumulation: their workgroups (two waves of up to 330 registers,
+// 28-56 KB of LDS) are then placed while the SIMDs are still free; queued behind it they waited for the accumulation to drain.
+template <class F>
+static hipError_t msm_queue_heavy_in_front(MsmEngine<F>& eng, MsmRunCall<F>& c, const MsmRunSchedule& s, int m) {
+  hipError_t e;
+  const hipStream_t st = c.st, st_reduce = c.st_reduces[m];
+  const bool on_reduce = s.heavy_on == 2 && st_reduce != st;
+  const bool side = !on_reduce && s.heavy_on != 0 && c.st_heavy && c.st_heavy != st;
+  c.heavy_first[m] = side || on_reduce;
+  c.heavy_stream[m] = on_reduce ? st_reduce : side ? c.st_heavy : st;
+  if (c.into(m)) {
+    // the bucket array is complete once the first MSM's redo pass has run (it follows that MSM's accumulation and
+    // heavy-bucket kernels on its reduction stream)
+    const hipEvent_t filled = eng.redo_done[c.bslot(m)];
+    if ((e = hipStreamWaitEvent(st, filled, 0)) != hipSuccess) return e;
+    if (c.heavy_stream[m] != st && (e = hipStreamWaitEvent(c.heavy_stream[m], filled, 0)) != hipSuccess) return e;
+    if (st_reduce != st && st_reduce != c.heavy_stream[m] && (e = hipStreamWaitEvent(st_reduce, filled, 0)) != hipSuccess) return e;
+  }
+  if (!c.heavy_first[m]) return hipSuccess;
+  e = msm_signal(eng.pre[c.slots[m]], st, c.heavy_stream[m]);
+  if (e == hipSuccess && !s.heavy_deferred) msm_launch_heavy(eng, c, s, m);
+  return e;
+}
+
+// The accumulation: one of the product's five launches (MsmAccumForm), per MSM or fused.
+template <class F>
+static void msm_launch_accum(const MsmRunCall<F>& c, const MsmRunSchedule& s) {
+  const uint32_t tot_b = s.tot_b;
+  for (int m = 0; m < (s.fused ? 1 : c.nm); m++) {
+#ifdef ZKMI_EXPERIMENTS
+    if (msm_exp_launch_accum(c, s, m)) continue;
+#endif
+    if constexpr (MsmEngineKernels<F>::LANES == 2) {
+      // a lane pair per bucket, or two (split2)
+      const MsmSort& sort = *c.sorts[m];
+      const bool split2 = s.accum == MSM_ACCUM_G2_SPLIT2;
+      hipLaunchKernelGGL((split2 ? &k_accum_g2_split2<0> : &k_accum_g2_nc<2, 1>), dim3(((split2 ? 4 : 2) * tot_b + 63) / 64), dim3(64), 0, c.st,
+                         c.bases[m], sort.begin, sort.count, sort.perm, sort.sorted, c.bk[m], tot_b, sort.plan.heavy_thr, c.redo[m]);
+    } else if (s.fused) {
+      // a lane per bucket, or two (split2); blockIdx.y = the MSM
+      const bool split2 = s.accum == MSM_ACCUM_G1_SPLIT2;
+      hipLaunchKernelGGL((split2 ? &k_accum_g1_split2<F, 1> : &k_accum_g1_nc<F, 3, 1, true>), dim3(((split2 ? 2 : 1) * tot_b + 63) / 64, c.nm),
+                         dim3(64), 0, c.st, c.fused_args(), tot_b);
+    } else {
+      const AccumArgs<F, false> one = {c.bases[m], c.bk[m], c.redo[m], c.view(m)};
+      hipLaunchKernelGGL((k_accum_g1_nc<F, 3, 1>), dim3((tot_b + 63) / 64), dim3(64), 0, c.st, one, tot_b);
+    }
+  }
+}
+
+// Behind the accumulation, MSM m: heavy kernels that run in line, the events that order the reduction stream behind both,
+// and the redo pass.  Everything that still reads the sort leaves an event in sort.readers: the next sort into these
+// buffers may be queued on another stream and must not overwrite what these kernels read.
+template <class F>
+static hipError_t msm_order_and_redo(MsmEngine<F>& eng, const MsmRunCall<F>& c, const MsmRunSchedule& s, int m) {
+  using K = MsmEngineKernels<F>;
+  hipError_t e;
+  const MsmSort& sort = *c.sorts[m];
+  const int slot = c.slots[m];
+  const hipStream_t st = c.st, st_reduce = c.st_reduces[m];
+  if (!c.heavy_first[m]) msm_launch_heavy(eng, c, s, m);
+  if ((e = msm_signal(eng.acc_done[slot], st, st_reduce, &sort)) != hipSuccess) return e;
+  // heavy kernels on a side stream; on the reduction's own stream redo_done below covers them too (same stream, later),
+  // which only the call-free kernels record
+  if (c.heavy_first[m] && (c.heavy_stream[m] != st_reduce || !s.nocall) &&
+      (e = msm_signal(eng.heavy_done[slot], c.heavy_stream[m], st_reduce, &sort)) != hipSuccess)
+    return e;
+  if (!s.nocall) return hipSuccess;
+  // after the accumulation (it writes the list), in front of the reduction (it reads the buckets);
+  // heavy buckets are never listed, so the heavy kernels may still be running
+  uint32_t* const redo = c.redo[m];
+  uint32_t* const ticket = redo + eng.cap_buckets + 1;
+  if (s.quad_redo)
+    hipLaunchKernelGGL(k_accum_redo_q<typename K::QPT>, dim3(64), dim3(64), 0, st_reduce, c.bases[m], sort.begin, sort.count, sort.sorted,
+                       c.bk[m], redo, ticket, c.into(m) ? 1u : 0u);
+  else if constexpr (K::LANES == 2)
+    hipLaunchKernelGGL(k_accum_redo_g2_split<0>, dim3(64), dim3(64), sizeof(XYZZ<F>) * 64 / K::LANES, st_reduce, c.bases[m], sort.begin,
+                       sort.count, sort.sorted, c.bk[m], redo, ticket);
+  else
+    hipLaunchKernelGGL(k_accum_redo<F>, dim3(64), dim3(64), sizeof(XYZZ<F>) * 64 / K::LANES, st_reduce, c.bases[m], sort.begin,
+                       sort.count, sort.sorted, c.bk[m], redo, ticket, c.into(m) ? 1u : 0u);
+  return msm_signal(eng.redo_done[slot], st_reduce, st_reduce, &sort);  // (the list reads the sort)
+}
+
+// The reduction of MSM m on its stream: segment sums, the optional second level, tree sums, the slot's `done` event.
+template <class F>
+static hipError_t msm_launch_reduction(MsmEngine<F>& eng, const MsmRunCall<F>& c, const MsmRunSchedule& s, int m) {
+  using K = MsmEngineKernels<F>;
+  using QPT = typename K::QPT;
+  using HF = typename MsmEngine<F>::HF;
+  constexpr int T = 256;
+  constexpr uint32_t SLOT_PTS = MsmEngine<F>::SLOT_PTS;
+  hipError_t e;
+  const int slot = c.slots[m];
+  const hipStream_t st_reduce = c.st_reduces[m];
+  const dim3 lists(s.njobs, c.sorts[0]->plan.nwin);
+  if (c.prof) c.prof->begin(c.ph_reduce, st_reduce);
+  XYZZ<F>* const bk = c.bk[m];
+  XYZZ<F>* const ssum = eng.segsum + (size_t)slot * eng.seg_cap;
+  XYZZ<F>* const sw = eng.segw + (size_t)slot * eng.seg_cap;
+  const XYZZ<F>*bk2 = nullptr, *bk3 = nullptr;
+  if (c.second(m)) {
+    // the other MSM's bucket array is complete behind its redo pass (which follows its accumulation and heavy-bucket kernels)
+    if ((e = hipStreamWaitEvent(st_reduce, eng.redo_done[c.bslot(m)], 0)) != hipSuccess) return e;
+    bk2 = eng.buckets + (size_t)c.bslot(m) * eng.cap_buckets;
+    if (c.third_slot >= 0) {
+      if ((e = hipStreamWaitEvent(st_reduce, eng.redo_done[c.third_slot], 0)) != hipSuccess) return e;
+      bk3 = eng.buckets + (size_t)c.third_slot * eng.cap_buckets;
+    }
+  }
+  if (s.quad_seg)
+    hipLaunchKernelGGL(k_segreduce_q<QPT>, dim3((s.tot_segs + QPT::PER_WAVE - 1) / QPT::PER_WAVE), dim3(64), 0, st_reduce, bk, ssum, sw,
+                       s.tot_segs, s.seg, bk2, bk3);
+  else if constexpr (K::LANES == 2)  // (the lane-pair segment sums have no second source)
+    hipLaunchKernelGGL(k_segreduce_g2_split<0>, dim3((K::LANES * s.tot_segs + T - 1) / T), dim3(T), 0, st_reduce, bk, ssum, sw, s.tot_segs, s.seg);
+  else  // (partitioned big windows: the two-wave build)
+    hipLaunchKernelGGL((s.wide ? &k_segreduce_w2<F> : &k_segreduce<F>), dim3((K::LANES * s.tot_segs + T - 1) / T), dim3(T), 0, st_reduce, bk,
+                       ssum, sw, s.tot_segs, s.seg, bk2, bk3);
+  TreeLevel2<XYZZ<F>> l2 = {nullptr, nullptr, 0u, -1};
+  if (s.level2) {
+    XYZZ<F>* const s2 = eng.seg2 + (size_t)slot * 2 * (eng.seg_cap >> MSM_SEG2_LOG);
+    XYZZ<F>* const t2 = s2 + (eng.seg_cap >> MSM_SEG2_LOG);
+    hipLaunchKernelGGL(K::segreduce2, dim3((K::LANES * s.tot_segs2 + T - 1) / T), dim3(T), 0, st_reduce, ssum, s2, t2, s.tot_segs2);
+    l2 = {s2, t2, s.segs2, s.t_job};
+  }
+  XYZZ<HF>* const dp = eng.partial + (size_t)slot * SLOT_PTS;
+  XYZZ<HF>* const hp_out = eng.h_partial + (size_t)slot * SLOT_PTS;  // pinned host slot, written by the tree-sum kernels themselves
+  XYZZ<F>* const stg = eng.tree_stage + (size_t)slot * MSM_STAGE_PTS;
+  if (s.quad_tree) {
+    hipLaunchKernelGGL(k_treesum_q<QPT>, dim3(lists.x, lists.y, s.nq), dim3(64), 0, st_reduce, ssum, sw, s.segs_per_win, dp, s.plain_job, stg, hp_out);
+    if (s.nq > 1) hipLaunchKernelGGL(k_treesum_final_q<QPT>, lists, dim3(64), 0, st_reduce, stg, s.nq, dp, hp_out);
+  } else {
+    auto treesum = K::treesum;
+#ifdef ZKMI_EXPERIMENTS
+    msm_exp_treesum_unsplit<F>(s, &treesum);
+#endif
+    hipLaunchKernelGGL(treesum, dim3(lists.x, lists.y, s.nchunk), dim3(s.tree_block), s.tree_lds, st_reduce, ssum, sw, s.segs_per_win, dp,
+                       s.plain_job, stg, hp_out, l2);
+    if (s.nchunk > 1)
+      hipLaunchKernelGGL(K::treesum_final, lists, dim3(s.final_block), s.final_lds, st_reduce, stg, s.nchunk, dp, hp_out);
+  }
+  if (c.prof) c.prof->end(c.ph_reduce, st_reduce);
+  // (the partials are in the pinned host slot when the last tree-sum kernel has finished: the event is all that is left)
+  return hipEventRecord(eng.done[slot], st_reduce);
+}
+
 template <class F>
 hipError_t MsmEngine<F>::run_device(const MsmSort& sort, const Affine<F>* d_bases, hipStream_t st,
                                     hipStream_t st_reduce, PhaseTimer* prof, int ph_accum, int ph_reduce, int slot,
@@ -1494,459 +1869,69 @@ hipError_t MsmEngine<F>::run_device(const MsmSort& sort, const Affine<F>* d_base
 //     k_accum_redo with into = 1) behind that event.
 // Either way its reduction yields the sum of both.  Both sorts must plan the same bucket set (checked by the caller: the
 // arrays are indexed by bucket id, and the ids mean the same digit values only under equal plans).
+//
+// Two invariants of the stages (stated here once):
+//   - every refusal happens before the first launch or event record: an early return between the accumulation and
+//     k_accum_redo would leave a redo list behind that the slot's next MSM appends to;
+//   - sort.readers receives, per MSM and in this order: acc_done; heavy_done where the heavy kernels ran on a side stream
+//     (or, with the retired accumulation kernels, on the reduction stream); redo_done.
 template <class F>
 hipError_t MsmEngine<F>::run_device_multi(const MsmSort* const* sorts, const Affine<F>* const* d_bases, int nm, hipStream_t st,
                                           const hipStream_t* st_reduces, PhaseTimer* prof, int ph_accum, int ph_reduce,
                                           const int* slots, hipStream_t st_heavy, const int* bucket_slots, int flags, int third_slot) {
+  constexpr bool is_g2 = MsmEngineKernels<F>::LANES == 2;
+  MsmRunCall<F> c = {sorts, d_bases, nm, st, st_reduces, prof, ph_accum, ph_reduce, slots, st_heavy, bucket_slots, flags, third_slot};
+  // ---- the arguments ----
   if (nm < 1 || nm > MSM_MULTI_MAX) return hipErrorInvalidValue;
   // third_slot >= 0 (with MSM_RUN_ADD_AT_REDUCE, one MSM): a THIRD bucket array joins the segment sums
-  if (third_slot >= nslots || (third_slot >= 0 && (nm != 1 || !(flags & MSM_RUN_ADD_AT_REDUCE) || !bucket_slots))) return hipErrorInvalidValue;
-  const bool no_reduce = (flags & MSM_RUN_NO_REDUCE) != 0;
-  // MSM_RUN_ADD_AT_REDUCE: bucket_slots[m] names a second SOURCE of this MSM's reduction (k_segreduce adds both arrays)
-  // instead of the array its kernels add INTO
-  const bool add_at_reduce = (flags & MSM_RUN_ADD_AT_REDUCE) != 0;
-  bool any_into = false;
+  if (third_slot >= nslots || (third_slot >= 0 && (nm != 1 || !c.add_at_reduce() || !bucket_slots))) return hipErrorInvalidValue;
+  c.any_into = false;
   for (int m = 0; m < nm; m++) {
     if (slots[m] < 0 || slots[m] >= nslots) return hipErrorInvalidValue;
     if (bucket_slots && (bucket_slots[m] < 0 || bucket_slots[m] >= nslots)) return hipErrorInvalidValue;
-    any_into = any_into || (!add_at_reduce && bucket_slots && bucket_slots[m] != slots[m]);
+    c.any_into = c.any_into || c.into(m);
   }
-  if (add_at_reduce && std::is_same<F, Fq2_28>::value) return hipErrorInvalidValue;  // (the lane-pair segment sums have no second source)
+  if (c.add_at_reduce() && is_g2) return hipErrorInvalidValue;  // (the lane-pair segment sums have no second source)
   // the accumulate-into forms exist for the call-free G1 kernels, one MSM per launch
-  if (any_into && (nm != 1 || std::is_same<F, Fq2_28>::value)) return hipErrorInvalidValue;
+  if (c.any_into && (nm != 1 || is_g2)) return hipErrorInvalidValue;
   const MsmPlan& pl = sorts[0]->plan;  // bucket count, windows, segment length: common to all (checked); heavy_thr is per sort
   for (int m = 1; m < nm; m++) {
     const MsmPlan& q = sorts[m]->plan;
     if (q.nwin != pl.nwin || q.nb != pl.nb || q.seg_log != pl.seg_log || q.shared != pl.shared || q.c != pl.c) return hipErrorInvalidValue;
   }
-  const uint32_t tot_b = pl.nwin * pl.nb;
-  const int T = 256;
-  hipError_t e;
-  // Heavy and light buckets are disjoint, so the heavy-bucket kernels only have to see the sort complete.  They run at the
-  // head of the REDUCTION's stream.  With uniform scalars the heavy list is empty, but an empty 512-workgroup launch still
-  // has to be placed: on a normal-priority stream it queued behind the next accumulation's workgroups (0.9 ms G1 / 9.8 ms
-  // G2 average in the round-2 trace) and every reduction waited for it.  The reduction streams have high priority, so
-  // there the launch is placed as soon as any workgroup retires, and no cross-stream event sits between it and the
-  // reduction.  (A/B library, ZKMI_HEAVY_ON: 0 = in line on the accumulation stream; 1 = on `st_heavy`, round 2's side stream.)
-  const int heavy_on = ZK_TUNE("ZKMI_HEAVY_ON", 2);
-  // The product's accumulation kernels are the call-free ones at 3 (G1) / 2 (G2) waves per SIMD.  A/B
-  // library: ZKMI_ACCUM / ZKMI_ACCUM_G2 = 0 | 1 select the retired generations (madd with an out-of-line doubling path),
-  // 2 | 3 the call-free kernels at 2 / 3 waves; ZKMI_ACCUM_BLOCK = 64 | 256 threads per workgroup and ZKMI_ACCUM_ROUNDS = R
-  // (every wave walks R load-ordered bucket groups) apply to the retired kernels.
-  const int accum_mode = ZK_TUNE("ZKMI_ACCUM", 3);
-  const int accum_mode_g2 = ZK_TUNE("ZKMI_ACCUM_G2", 2);
-  const int mode = std::is_same<F, Fq2_28>::value ? accum_mode_g2 : accum_mode;
-  const bool nocall = mode == 2 || mode == 3;
-  // The reduction-side kernels with every complete addition split over a lane quad (msm_quad.hpp; G1 and BN254 G1): bit 0 =
-  // segment sums, 1 = tree sums, 2 = redo pass, 3 = the summing of heavy-bucket partials.  One-wave workgroups at the
-  // accumulation kernels' register count: placed beside them.  (A/B library: ZKMI_QUAD = mask; 0 = the one-lane kernels.)
-  // The partitioned big windows keep the one-lane segment and tree sums: their reduction has the chip to itself.
-  // Two contexts: ONE MSM or ONE proof by itself (host_spin: the latency path -- a chain of 4 products per dependent addition
-  // instead of 14) and the batch prover's pipeline (throughput: the quad form issues 16 products for the 14 of the formula
-  // plus its exchanges, 1.37 x the instructions of the one-lane addition).
-  // G2 (the octet form, 8 lanes per point): ZKMI_QUAD_G2 / ZKMI_QUAD_G2_BATCH.
-  constexpr bool g2_engine = std::is_same<F, Fq2_28>::value;
-  const int quad_mask = g2_engine ? (host_spin ? ZK_TUNE("ZKMI_QUAD_G2", 15) : ZK_TUNE("ZKMI_QUAD_G2_BATCH", 12))
-                                  : (host_spin ? ZK_TUNE("ZKMI_QUAD", 15) : ZK_TUNE("ZKMI_QUAD_BATCH", 12));
-  using QPT = typename std::conditional<g2_engine, XYZZQ<Fq28, 0, true>, XYZZQ<F, 0, false>>::type;
-  constexpr uint32_t QPW = g2_engine ? 8u : 16u;  // points per wave of the quad / octet kernels
-  const bool quad_reduce_ok = pl.shared || pl.c <= 16;
-#ifdef ZKMI_EXPERIMENTS
-  const int accum_block = ZK_TUNE("ZKMI_ACCUM_BLOCK", 64) == 256 ? 256 : 64;
-  const int accum_rounds = ZK_TUNE("ZKMI_ACCUM_ROUNDS", 0);
-  auto striped = [&](uint32_t threads_needed, uint32_t block) {
-    uint32_t blocks = (threads_needed + block - 1) / block;
-    if (accum_rounds > 1) blocks = (blocks + accum_rounds - 1) / accum_rounds;
-    return blocks ? blocks : 1u;
-  };
-#else
-  if (!nocall) return hipErrorInvalidValue;  // (unreachable: the defaults above are compiled in)
-#endif
-  if (any_into && !nocall) return hipErrorInvalidValue;
-  auto bslot_of = [&](int m) { return bucket_slots ? bucket_slots[m] : slots[m]; };
-  auto into_of = [&](int m) { return !add_at_reduce && bslot_of(m) != slots[m]; };
-  auto second_of = [&](int m) { return add_at_reduce && bslot_of(m) != slots[m]; };
-  auto bk_of = [&](int m) { return buckets + (size_t)(into_of(m) ? bslot_of(m) : slots[m]) * cap_buckets; };
-  // everything the reductions below would refuse is refused here, before the first launch: an early return between the
-  // accumulation and k_accum_redo would leave a redo list behind that the slot's next MSM appends to
-  {
-    const uint32_t spw = pl.nb >> pl.seg_log;
-    if ((uint64_t)pl.nwin * spw > seg_cap || (uint64_t)(2 + msm_seg_bits(pl)) * pl.nwin > SLOT_PTS || tot_b > cap_buckets)
-      return hipErrorInvalidValue;
+  // ---- the schedule, and what the buffers cannot hold ----
+  const MsmRunSchedule s = msm_run_schedule(pl, MsmEngineKernels<F>::KIND, host_spin, nm, flags, c.any_into);
+  if (c.any_into && !s.nocall) return hipErrorInvalidValue;
+  if (s.tot_segs > seg_cap || (uint64_t)(2 + s.seg_bits) * pl.nwin > SLOT_PTS || s.tot_b > cap_buckets) return hipErrorInvalidValue;
+  for (int m = 0; m < nm; m++) {
+    c.bk[m] = buckets + (size_t)(c.into(m) ? c.bslot(m) : slots[m]) * cap_buckets;
+    c.redo[m] = redo + (size_t)slots[m] * (cap_buckets + 2);
   }
-  // [0] length, [1 ..] list, [cap_buckets + 1] ticket (k_accum_redo)
-  auto redo_of = [&](int m) { return this->redo + (size_t)slots[m] * (cap_buckets + 2); };
-
-  // ---- in front of the accumulation: heavy-bucket kernels of every MSM that runs them on another stream ----
-  // On another stream they are queued BEFORE the accumulation: their workgroups (two waves of up to 330 registers, 28-56 KB
-  // of LDS) are then placed while the SIMDs are still free; queued behind it they waited for the accumulation to drain.
-  bool heavy_first[MSM_MULTI_MAX];
-  hipStream_t heavy_stream[MSM_MULTI_MAX];
-  // (A/B library, ZKMI_HEAVY_DEFER=1: one small proof / MSM by itself queues its heavy launches BEHIND the accumulation launch --
-  // still ordered behind the sort only -- so that the accumulation, the longest link, is submitted ~50 us per MSM earlier.
-  // Measured in round 6: no gain, 2^14 - 2^15 slightly worse; g2_split2_ab.txt)
-  const bool heavy_deferred = host_spin && tot_b <= (1u << 16) && (quad_mask & 8) && heavy_on == 2 && ZK_TUNE("ZKMI_HEAVY_DEFER", 0) != 0;
-  auto launch_heavy = [&](int m) {
-    const MsmSort& sort = *sorts[m];
-    // MSMs of different slots may overlap: partial sums, plan and tickets per slot
-    XYZZ<F>* const hp = heavy_partial + (size_t)slots[m] * ((size_t)MSM_HPOOL + MSM_HNC_POOL);
-    XYZZ<F>* const pool_nc = hp + MSM_HPOOL;
-    uint32_t* const hplan = heavy_plan + (size_t)slots[m] * MSM_HPLAN_WORDS;
-    uint32_t* const tk = heavy_ticket + (size_t)slots[m] * MSM_HEAVY_CAP;
-    const bool wide_tail = !pl.shared && pl.c > 16;  // partitioned big windows: see k_accum_heavy
-    // the call-free kernels take the additions of points (DESIGN.md 4.1 "heavy buckets"); not for lists the plan cannot
-    // hold (decided on the device), the partitioned big windows' thousands of entries, or the A/B accumulate-into forms
-    // (A/B library: ZKMI_HEAVY_NC=0 = the complete-law kernel of rounds 1-4 for everything)
-    const bool nc = ZK_TUNE("ZKMI_HEAVY_NC", 1) != 0 && !wide_tail && !into_of(m);
-    constexpr uint32_t lanes = std::is_same<F, Fq2_28>::value ? 32u : 64u;
-    if (nc) {
-      hipLaunchKernelGGL(k_heavy_plan<0>, dim3(1), dim3(64), 0, heavy_stream[m], sort.heavy, sort.count, sort.begin, hplan, lanes, 0u);
-      // one-wave workgroups, grid-strided over the wave-items: twice the chip's wave slots (an empty list costs one placement)
-      if constexpr (std::is_same<F, Fq2_28>::value)
-        hipLaunchKernelGGL((k_accum_heavy_nc_g2<2>), dim3(4096), dim3(64), 0, heavy_stream[m], d_bases[m], sort.sorted, hplan, pool_nc);
-      else
-        hipLaunchKernelGGL((k_accum_heavy_nc<F, 3>), dim3(6144), dim3(64), 0, heavy_stream[m], d_bases[m], sort.sorted, hplan, pool_nc);
-    }
-    const uint32_t* const plan_arg = nc ? hplan : nullptr;
-    if (nc && (quad_mask & 8)) {
-      // both modes of the plan in one-wave workgroups of quads / octets: nothing of 300 registers has to find a SIMD beside the accumulation
-      hipLaunchKernelGGL(k_heavy_q<QPT>, dim3(1024), dim3(64), 0, heavy_stream[m], d_bases[m], sort.begin, sort.count, sort.heavy,
-                         sort.sorted, bk_of(m), hp, tk, hplan, pool_nc);
-    } else if constexpr (std::is_same<F, Fq2_28>::value) {
-      hipLaunchKernelGGL(k_accum_heavy_g2_split<0>, dim3(MSM_HSPLIT, 8), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T / 2, heavy_stream[m],
-                         d_bases[m], sort.begin, sort.count, sort.heavy, sort.sorted, bk_of(m), hp, tk, 0u,
-                         wide_tail ? MSM_HEAVY_CAP : 0xffffffffu, plan_arg, pool_nc);
-      if (wide_tail)
-        hipLaunchKernelGGL(k_accum_heavy_g2_split<0>, dim3(1, 4096), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T / 2, heavy_stream[m],
-                           d_bases[m], sort.begin, sort.count, sort.heavy, sort.sorted, bk_of(m), hp, tk, MSM_HEAVY_CAP, 0xffffffffu,
-                           (const uint32_t*)nullptr, pool_nc);
-    } else {
-      hipLaunchKernelGGL(k_accum_heavy<F>, dim3(MSM_HSPLIT, 8), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T, heavy_stream[m],
-                         d_bases[m], sort.begin, sort.count, sort.heavy, sort.sorted, bk_of(m), hp, tk, into_of(m) ? 1u : 0u, 0u,
-                         wide_tail ? MSM_HEAVY_CAP : 0xffffffffu, plan_arg, pool_nc);
-      if (wide_tail)
-        hipLaunchKernelGGL(k_accum_heavy<F>, dim3(1, 4096), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T, heavy_stream[m],
-                           d_bases[m], sort.begin, sort.count, sort.heavy, sort.sorted, bk_of(m), hp, tk, into_of(m) ? 1u : 0u, MSM_HEAVY_CAP,
-                           0xffffffffu, (const uint32_t*)nullptr, pool_nc);
-    }
-  };
 #ifdef ZKMI_EXPERIMENTS
-  if (const int mask_bits = ZK_TUNE("ZKMI_GATHER_MASK_BITS", 0); mask_bits > 0 && mask_bits < 31)
-    for (int m = 0; m < nm; m++)  // (all cap_entries words of the buffer: idempotent, and a sort may serve several MSMs)
-      hipLaunchKernelGGL(k_mask_sorted<0>, dim3(1024), dim3(256), 0, st, sorts[m]->sorted, sorts[m]->cap_entries,
-                         0x80000000u | ((1u << mask_bits) - 1u));
+  msm_exp_mask_sorted(c, s);
+#else
+  // (the retired accumulation kernels and the accumulate-into kernel are A/B variants: the product adds at the reduction)
+  if (!s.nocall || c.any_into) return hipErrorInvalidValue;
 #endif
-  // second running-sum level: the one-lane segment and tree sums of shared-bucket plans whose windows have a segment list
-  // long enough for one (the quad / octet kernels, the windowed plans and their exchange layouts keep the single level)
-  const bool level2 = pl.shared && !(quad_mask & 3) && (pl.nb >> pl.seg_log) >= MSM_SEG2_MIN_SEGS;
+  hipError_t e;
+  // ---- in front of the accumulation: heavy-bucket kernels of every MSM that runs them on another stream ----
   for (int m = 0; m < nm; m++) {
     slot_plan[slots[m]] = sorts[m]->plan;
-    slot_plan[slots[m]].seg2_log = level2 ? MSM_SEG2_LOG : 0;
-    const hipStream_t st_reduce = st_reduces[m];
-    const bool on_reduce = heavy_on == 2 && st_reduce != st;
-    const bool side = !on_reduce && heavy_on != 0 && st_heavy && st_heavy != st;
-    heavy_first[m] = side || on_reduce;
-    heavy_stream[m] = on_reduce ? st_reduce : side ? st_heavy : st;
-    if (into_of(m)) {
-      // the bucket array is complete once the first MSM's redo pass has run (it follows that MSM's accumulation and
-      // heavy-bucket kernels on its reduction stream)
-      if ((e = hipStreamWaitEvent(st, redo_done[bslot_of(m)], 0)) != hipSuccess) return e;
-      if (heavy_stream[m] != st && (e = hipStreamWaitEvent(heavy_stream[m], redo_done[bslot_of(m)], 0)) != hipSuccess) return e;
-      if (st_reduce != st && st_reduce != heavy_stream[m] && (e = hipStreamWaitEvent(st_reduce, redo_done[bslot_of(m)], 0)) != hipSuccess) return e;
-    }
-    if (heavy_first[m]) {
-      if ((e = hipEventRecord(pre[slots[m]], st)) != hipSuccess) return e;
-      if ((e = hipStreamWaitEvent(heavy_stream[m], pre[slots[m]], 0)) != hipSuccess) return e;
-      if (!heavy_deferred) launch_heavy(m);
-    }
+    slot_plan[slots[m]].seg2_log = s.seg2_log;
+    if ((e = msm_queue_heavy_in_front(*this, c, s, m)) != hipSuccess) return e;
   }
-  auto view_of = [&](int m) {
-    const MsmSort& sort = *sorts[m];
-    return SortView{sort.begin, sort.count, sort.perm, sort.sorted, sort.plan.heavy_thr};
-  };
-
-  // ---- the accumulation ----
-  // A/B library test switch ZKMI_FORCE_MULTI: a lone MSM through the multi-MSM launch too (so that the generic MSM entry
-  // points, with their degenerate inputs -- repeated bases, P + (-P), points at infinity --, reach k_accum_g1_split2 / the
-  // MULTI kernel form)
-  const bool force_multi = ZK_TUNE("ZKMI_FORCE_MULTI", 0) != 0;
+  // ---- the accumulation (the phase brackets its launches only: roofline leg of bench.py) ----
   if (prof) prof->begin(ph_accum, st);
-  if constexpr (std::is_same<F, Fq2_28>::value) {
-    for (int m = 0; m < nm; m++) {
-      const MsmSort& sort = *sorts[m];
-      const uint32_t heavy_thr = sort.plan.heavy_thr;
-      XYZZ<F>* const bk = bk_of(m);
-      uint32_t* const redo = redo_of(m);
-#ifdef ZKMI_EXPERIMENTS
-      if (mode == 3) {
-        hipLaunchKernelGGL((k_accum_g2_nc<3, 1>), dim3((2 * tot_b + 63) / 64), dim3(64), 0, st, d_bases[m], sort.begin, sort.count,
-                           sort.perm, sort.sorted, bk, tot_b, heavy_thr, redo);
-        continue;
-      }
-      if (mode != 2) {
-        if (accum_block == 64)
-          hipLaunchKernelGGL(k_accum_g2_split<1>, dim3(striped(2 * tot_b, 64)), dim3(64), 0, st, d_bases[m], sort.begin, sort.count,
-                             sort.perm, sort.sorted, bk, tot_b, heavy_thr);
-        else
-          hipLaunchKernelGGL(k_accum_g2_split<4>, dim3(striped(2 * tot_b, 256)), dim3(256), 0, st, d_bases[m], sort.begin, sort.count,
-                             sort.perm, sort.sorted, bk, tot_b, heavy_thr);
-        continue;
-      }
-#endif
-#ifdef ZKMI_EXPERIMENTS
-      if ((quad_mask & 16) && tot_b <= (1u << 16)) {
-        // one small MSM by itself: an octet per bucket (msm_quad.hpp k_accum_q) -- 4 products per entry instead of 10
-        if constexpr (g2_engine) {
-          AccumQArgs<QPT> qa;
-          for (int k = 0; k < MSM_MULTI_MAX; k++) {
-            qa.bases[k] = d_bases[m];
-            qa.buckets[k] = bk;
-            qa.sort[k] = view_of(m);
-          }
-          hipLaunchKernelGGL(k_accum_q<QPT>, dim3((tot_b + QPW - 1) / QPW, 1), dim3(64), 0, st, qa, tot_b);
-        }
-        continue;
-      }
-#endif
-      if (host_spin && tot_b <= (1u << 15) && ZK_TUNE("ZKMI_SOLO_SPLIT_G2", 1) != 0) {
-        // one small G2 MSM by itself (the G2 launch of a single small proof): two lane pairs per bucket halve the chain
-        // (2^13 1.99 -> 1.74 ms, 2^14 1.92 -> 1.77, 2^15 2.38 -> 2.2; at 2^16 buckets the chip is full and it costs 0.08 ms:
-        // profiles/r06/experiments/g2_split2_ab.txt)
-        hipLaunchKernelGGL(k_accum_g2_split2<0>, dim3((4 * tot_b + 63) / 64), dim3(64), 0, st, d_bases[m], sort.begin, sort.count,
-                           sort.perm, sort.sorted, bk, tot_b, heavy_thr, redo);
-        continue;
-      }
-      hipLaunchKernelGGL((k_accum_g2_nc<2, 1>), dim3((2 * tot_b + 63) / 64), dim3(64), 0, st, d_bases[m], sort.begin, sort.count,
-                         sort.perm, sort.sorted, bk, tot_b, heavy_thr, redo);
-    }
-  } else if ((nm > 1 || (force_multi && !any_into)) && nocall) {
-    AccumArgs<F, true> set;
-    for (int m = 0; m < MSM_MULTI_MAX; m++) {
-      const int k = m < nm ? m : 0;
-      set.bases_[m] = d_bases[k];
-      set.buckets_[m] = bk_of(k);
-      set.redo_[m] = redo_of(k);
-      set.sort_[m] = view_of(k);
-    }
-    // small plans (one small proof): two lanes per bucket (A/B library: ZKMI_SOLO_SPLIT=0: one)
-    const bool split2 = ZK_TUNE("ZKMI_SOLO_SPLIT", 1) != 0;
-#ifdef ZKMI_EXPERIMENTS
-    if ((quad_mask & 16) && tot_b <= (1u << 16)) {
-      // a quad per bucket (msm_quad.hpp k_accum_q): the complete law in line, no redo list
-      if constexpr (!g2_engine) {
-        AccumQArgs<QPT> qa;
-        for (int m = 0; m < MSM_MULTI_MAX; m++) {
-          const int k = m < nm ? m : 0;
-          qa.bases[m] = d_bases[k];
-          qa.buckets[m] = bk_of(k);
-          qa.sort[m] = view_of(k);
-        }
-        hipLaunchKernelGGL(k_accum_q<QPT>, dim3((tot_b + QPW - 1) / QPW, nm), dim3(64), 0, st, qa, tot_b);
-      }
-    } else
-#endif
-    if (split2 && tot_b <= (1u << 16))
-      hipLaunchKernelGGL((k_accum_g1_split2<F, 1>), dim3((2 * tot_b + 63) / 64, nm), dim3(64), 0, st, set, tot_b);
-#ifdef ZKMI_EXPERIMENTS
-    else if (accum_mode != 3)
-      hipLaunchKernelGGL((k_accum_g1_nc<F, 2, 1, true>), dim3((tot_b + 63) / 64, nm), dim3(64), 0, st, set, tot_b);
-#endif
-    else
-      hipLaunchKernelGGL((k_accum_g1_nc<F, 3, 1, true>), dim3((tot_b + 63) / 64, nm), dim3(64), 0, st, set, tot_b);
-  } else {
-    for (int m = 0; m < nm; m++) {
-      const MsmSort& sort = *sorts[m];
-      XYZZ<F>* const bk = bk_of(m);
-      uint32_t* const redo = redo_of(m);
-      const AccumArgs<F, false> one = {d_bases[m], bk, redo, view_of(m)};
-      if (into_of(m)) {
-#ifdef ZKMI_EXPERIMENTS
-        hipLaunchKernelGGL((k_accum_g1_nc<F, 3, 1, false, true>), dim3((tot_b + 63) / 64), dim3(64), 0, st, one, tot_b);
-        continue;
-#else
-        return hipErrorInvalidValue;  // (the accumulate-into kernel is an A/B variant: the product adds at the reduction)
-#endif
-      }
-#ifdef ZKMI_EXPERIMENTS
-      if (accum_mode != 3) {
-        const uint32_t heavy_thr = sort.plan.heavy_thr;
-        const dim3 grid((tot_b + T - 1) / T);
-        if (accum_mode == 2)
-          hipLaunchKernelGGL((k_accum_g1_nc<F, 2, 1>), dim3((tot_b + 63) / 64), dim3(64), 0, st, one, tot_b);
-        else if (accum_mode == 1)
-          hipLaunchKernelGGL(k_accum<F>, grid, dim3(T), 0, st, d_bases[m], sort.begin, sort.count, sort.perm, sort.sorted, bk, tot_b,
-                             heavy_thr);
-        else if (accum_block == 64)
-          hipLaunchKernelGGL((k_accum_g1_glds<F, 1>), dim3(striped(tot_b, 64)), dim3(64), 0, st, d_bases[m], sort.begin, sort.count,
-                             sort.perm, sort.sorted, bk, tot_b, heavy_thr);
-        else
-          hipLaunchKernelGGL((k_accum_g1_glds<F, 4>), dim3(striped(tot_b, 256)), dim3(256), 0, st, d_bases[m], sort.begin, sort.count,
-                             sort.perm, sort.sorted, bk, tot_b, heavy_thr);
-        continue;
-      }
-#endif
-      (void)sort;
-#ifdef ZKMI_EXPERIMENTS
-      // (A/B library: the occupancy-capped kernel of the pipelined big MSM -- msm_pipe.hpp, measured neutral -- or, with
-      // ZKMI_ACCUM_W2=1, for every lone G1 accumulation: 12 % slower than three waves)
-      if ((flags & MSM_RUN_TWO_WAVES) || ZK_TUNE("ZKMI_ACCUM_W2", 0) == 1) {
-        hipLaunchKernelGGL(k_accum_g1_nc_w2<F>, dim3((tot_b + 63) / 64), dim3(64), 0, st, one, tot_b);
-        continue;
-      }
-#endif
-      hipLaunchKernelGGL((k_accum_g1_nc<F, 3, 1>), dim3((tot_b + 63) / 64), dim3(64), 0, st, one, tot_b);
-    }
-  }
-  if (prof) prof->end(ph_accum, st);  // the phase brackets the accumulation launch(es) only (roofline leg of bench.py)
-  if (heavy_deferred)
-    for (int m = 0; m < nm; m++)
-      if (heavy_first[m]) launch_heavy(m);
-
-  // ---- behind it, per MSM: heavy kernels that run in line, redo list, reduction, copy of the partials ----
-  const uint32_t segs_per_win = pl.nb >> pl.seg_log;
-  const uint32_t tot_segs = pl.nwin * segs_per_win;
-  const int seg = 1 << pl.seg_log;
-  const uint32_t segs2 = segs_per_win >> MSM_SEG2_LOG, tot_segs2 = tot_segs >> MSM_SEG2_LOG;  // (level2 only)
-  const int njobs = msm_njobs(slot_plan[slots[0]]);
-  const int plain_job = pl.shared ? njobs - 1 : -1;
-  const int t_job = level2 ? njobs - 2 : -1;
-  // small plans: the job lists are cut into slices of two segments per thread or lane pair (k_treesum_final adds the slices)
-  constexpr bool is_g2 = std::is_same<F, Fq2_28>::value;
-  const uint32_t per_block = is_g2 ? MSM_TREE_T : 2 * MSM_TREE_T;  // G2: 64 lane pairs x 2 segments
-  uint32_t nchunk = 1;
-  if (tot_b <= (1u << 16) && segs_per_win > per_block) {
-    nchunk = segs_per_win / per_block;
-    if (nchunk > MSM_TREE_T) nchunk = MSM_TREE_T;
-    // (fewer, longer slices -- at most 16, 8 or 4 -- measured the same group rates and single-proof latencies within noise:
-    // profiles/r05/experiments/tree_slices_ab.txt)
-    if ((uint64_t)njobs * pl.nwin * nchunk > MSM_STAGE_PTS_1) nchunk = 1;
-  } else if (!pl.shared && tot_b <= (1u << 19) && segs_per_win > per_block) {
-    // one windowed MSM of up to 2^19 buckets: as many slices as the stage holds (16 windows x 13 jobs: 16), see plan_set_heavy
-    // (... and as the chip holds at once: 3 328 workgroups of 9 dependent additions each, in three rounds, took longer than 208 of 23)
-    nchunk = MSM_TREE_T;
-    while (nchunk > 1 && ((uint64_t)njobs * pl.nwin * nchunk > 1024 || nchunk * per_block > segs_per_win)) nchunk >>= 1;
-  } else if (!pl.shared && pl.c > 16) {
-    // partitioned big windows: 2^(c-5) segments per (window, job) list on ONE workgroup are a chain of 2^(c-12) dependent
-    // additions (5 ms at c = 20); sliced, as many slices as the stage holds (16 at 13 windows x 16 jobs)
-    nchunk = MSM_TREE_T;
-    while (nchunk > 1 && ((uint64_t)njobs * pl.nwin * nchunk > MSM_STAGE_PTS_1 || nchunk * per_block > segs_per_win)) nchunk >>= 1;
-  }
+  msm_launch_accum(c, s);
+  if (prof) prof->end(ph_accum, st);
+  for (int m = 0; m < nm && s.heavy_deferred; m++)
+    if (c.heavy_first[m]) msm_launch_heavy(*this, c, s, m);
+  // ---- behind it, per MSM: heavy kernels that run in line, events, redo pass, reduction ----
   for (int m = 0; m < nm; m++) {
-    const MsmSort& sort = *sorts[m];
-    const int slot = slots[m];
-    const hipStream_t st_reduce = st_reduces[m];
-    XYZZ<F>* const bk = bk_of(m);
-    if (!heavy_first[m]) launch_heavy(m);
-    if ((e = hipEventRecord(acc_done[slot], st)) != hipSuccess) return e;
-    sort.readers.push_back(acc_done[slot]);  // the next sort into these buffers may be queued on another stream
-    if (st_reduce != st && (e = hipStreamWaitEvent(st_reduce, acc_done[slot], 0)) != hipSuccess) return e;
-    if (heavy_first[m] && heavy_stream[m] != st_reduce) {  // side stream
-      if ((e = hipEventRecord(heavy_done[slot], heavy_stream[m])) != hipSuccess) return e;
-      if ((e = hipStreamWaitEvent(st_reduce, heavy_done[slot], 0)) != hipSuccess) return e;
-      sort.readers.push_back(heavy_done[slot]);  // the next sort must not overwrite what these kernels read
-    }
-    if (heavy_first[m] && heavy_stream[m] == st_reduce && !nocall) {  // (with the call-free kernels redo_done below covers the heavy kernels too: same stream, later)
-      if ((e = hipEventRecord(heavy_done[slot], st_reduce)) != hipSuccess) return e;
-      sort.readers.push_back(heavy_done[slot]);
-    }
-    if (nocall) {
-      // after the accumulation (it writes the list), in front of the reduction (it reads the buckets);
-      // heavy buckets are never listed, so the heavy kernels may still be running
-      uint32_t* const redo = redo_of(m);
-      if (quad_mask & 4)
-        hipLaunchKernelGGL(k_accum_redo_q<QPT>, dim3(64), dim3(64), 0, st_reduce, d_bases[m], sort.begin, sort.count, sort.sorted, bk, redo,
-                           redo + cap_buckets + 1, into_of(m) ? 1u : 0u);
-      else if constexpr (std::is_same<F, Fq2_28>::value)
-        hipLaunchKernelGGL(k_accum_redo_g2_split<0>, dim3(64), dim3(64), sizeof(XYZZ<F>) * 32, st_reduce, d_bases[m], sort.begin, sort.count, sort.sorted, bk,
-                           redo, redo + cap_buckets + 1);
-      else
-        hipLaunchKernelGGL(k_accum_redo<F>, dim3(64), dim3(64), sizeof(XYZZ<F>) * 64, st_reduce, d_bases[m], sort.begin, sort.count, sort.sorted, bk, redo,
-                           redo + cap_buckets + 1, into_of(m) ? 1u : 0u);
-      // the list reads the sort: the next sort must wait for this kernel too
-      if ((e = hipEventRecord(redo_done[slot], st_reduce)) != hipSuccess) return e;
-      sort.readers.push_back(redo_done[slot]);
-    }
-    if (no_reduce) continue;  // a later MSM adds into these buckets and reduces them (bucket_slots)
-    if (prof) prof->begin(ph_reduce, st_reduce);
-    XYZZ<F>* const ssum = segsum + (size_t)slot * seg_cap;
-    XYZZ<F>* const sw = segw + (size_t)slot * seg_cap;
-    if constexpr (is_g2) {
-      if ((quad_mask & 1) && quad_reduce_ok)
-        hipLaunchKernelGGL(k_segreduce_q<QPT>, dim3((tot_segs + QPW - 1) / QPW), dim3(64), 0, st_reduce, bk, ssum, sw, tot_segs, seg,
-                           (const XYZZ<F>*)nullptr, (const XYZZ<F>*)nullptr);
-      else
-        hipLaunchKernelGGL(k_segreduce_g2_split<0>, dim3((2 * tot_segs + T - 1) / T), dim3(T), 0, st_reduce, bk, ssum, sw,
-                           tot_segs, seg);
-    } else {
-      const XYZZ<F>*bk2 = nullptr, *bk3 = nullptr;
-      if (second_of(m)) {
-        // the other MSM's bucket array is complete behind its redo pass (which follows its accumulation and heavy-bucket kernels)
-        if ((e = hipStreamWaitEvent(st_reduce, redo_done[bslot_of(m)], 0)) != hipSuccess) return e;
-        bk2 = buckets + (size_t)bslot_of(m) * cap_buckets;
-        if (third_slot >= 0) {
-          if ((e = hipStreamWaitEvent(st_reduce, redo_done[third_slot], 0)) != hipSuccess) return e;
-          bk3 = buckets + (size_t)third_slot * cap_buckets;
-        }
-      }
-      if (!pl.shared && pl.c > 16)
-        hipLaunchKernelGGL(k_segreduce_w2<F>, dim3((tot_segs + T - 1) / T), dim3(T), 0, st_reduce, bk, ssum, sw, tot_segs, seg, bk2, bk3);
-      else if (quad_mask & 1)
-        hipLaunchKernelGGL(k_segreduce_q<QPT>, dim3((tot_segs + QPW - 1) / QPW), dim3(64), 0, st_reduce, bk, ssum, sw, tot_segs, seg, bk2, bk3);
-      else
-        hipLaunchKernelGGL(k_segreduce<F>, dim3((tot_segs + T - 1) / T), dim3(T), 0, st_reduce, bk, ssum, sw, tot_segs, seg, bk2, bk3);
-    }
-    TreeLevel2<XYZZ<F>> l2 = {nullptr, nullptr, 0u, -1};
-    if (level2) {
-      XYZZ<F>* const s2 = seg2 + (size_t)slot * 2 * (seg_cap >> MSM_SEG2_LOG);
-      XYZZ<F>* const t2 = s2 + (seg_cap >> MSM_SEG2_LOG);
-      if constexpr (is_g2)
-        hipLaunchKernelGGL(k_segreduce2_g2_split<0>, dim3((2 * tot_segs2 + T - 1) / T), dim3(T), 0, st_reduce, ssum, s2, t2, tot_segs2);
-      else
-        hipLaunchKernelGGL(k_segreduce2<F>, dim3((tot_segs2 + T - 1) / T), dim3(T), 0, st_reduce, ssum, s2, t2, tot_segs2);
-      l2 = {s2, t2, segs2, t_job};
-    }
-    XYZZ<HF>* dp = partial + (size_t)slot * SLOT_PTS;
-    XYZZ<HF>* const hp_out = h_partial + (size_t)slot * SLOT_PTS;  // pinned host slot, written by the tree-sum kernels themselves
-    XYZZ<F>* const stg = tree_stage + (size_t)slot * MSM_STAGE_PTS;
-    if ((quad_mask & 2) && quad_reduce_ok) {
-      // one wave (16 quads / 8 octets) per slice of a job list; as many slices as make the two levels equally deep (a point
-      // walks len / (PER_WAVE slices) segments, the final sum slices / PER_WAVE), within the stage
-      uint32_t nq = 1;
-      while ((uint64_t)nq * nq * 4 <= segs_per_win) nq <<= 1;  // ~ sqrt(segs_per_win), rounded to a power of two
-      while (nq > 1 && ((uint64_t)njobs * pl.nwin * nq > MSM_STAGE_PTS || nq * QPW > segs_per_win)) nq >>= 1;
-      hipLaunchKernelGGL(k_treesum_q<QPT>, dim3(njobs, pl.nwin, nq), dim3(64), 0, st_reduce, ssum, sw, segs_per_win, dp, plain_job, stg, hp_out);
-      if (nq > 1) hipLaunchKernelGGL(k_treesum_final_q<QPT>, dim3(njobs, pl.nwin), dim3(64), 0, st_reduce, stg, nq, dp, hp_out);
-    } else if constexpr (is_g2) {
-      if (nchunk > 1) {
-        hipLaunchKernelGGL(k_treesum_g2_split<0>, dim3(njobs, pl.nwin, nchunk), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T / 2, st_reduce,
-                           ssum, sw, segs_per_win, dp, plain_job, stg, hp_out, l2);
-        uint32_t tf = 64;
-        while (tf < 2 * nchunk) tf <<= 1;
-        hipLaunchKernelGGL(k_treesum_final_g2_split<0>, dim3(njobs, pl.nwin), dim3(tf), sizeof(XYZZ<F>) * tf / 2, st_reduce, stg, nchunk, dp, hp_out);
-      } else {
-        // big plans: the same lane-pair kernel, 128 pairs per job (the unsplit form's 330-register additions made this the
-        // slowest link of a proof's tail: 16 + 7 dependent additions of 45-60 us); A/B library, ZKMI_G2_TREE_SPLIT=0: the unsplit kernel
-#ifdef ZKMI_EXPERIMENTS
-        if (ZK_TUNE("ZKMI_G2_TREE_SPLIT", 1) == 0)
-          hipLaunchKernelGGL(k_treesum<F>, dim3(njobs, pl.nwin, 1), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T, st_reduce,
-                             ssum, sw, segs_per_win, dp, plain_job, stg, hp_out, l2);
-        else
-#endif
-          hipLaunchKernelGGL(k_treesum_g2_split<0>, dim3(njobs, pl.nwin, 1), dim3(2 * MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T, st_reduce,
-                             ssum, sw, segs_per_win, dp, plain_job, stg, hp_out, l2);
-      }
-    } else {
-      hipLaunchKernelGGL(k_treesum<F>, dim3(njobs, pl.nwin, nchunk), dim3(MSM_TREE_T), sizeof(XYZZ<F>) * MSM_TREE_T, st_reduce,
-                         ssum, sw, segs_per_win, dp, plain_job, stg, hp_out, l2);
-      if (nchunk > 1) {
-        uint32_t tf = 64;
-        while (tf < nchunk) tf <<= 1;
-        hipLaunchKernelGGL(k_treesum_final<F>, dim3(njobs, pl.nwin), dim3(tf), sizeof(XYZZ<F>) * tf, st_reduce, stg, nchunk, dp, hp_out);
-      }
-    }
-    if (prof) prof->end(ph_reduce, st_reduce);
-    // (the partials are in the pinned host slot when the last tree-sum kernel has finished: the event is all that is left)
-    if ((e = hipEventRecord(done[slot], st_reduce)) != hipSuccess) return e;
+    if ((e = msm_order_and_redo(*this, c, s, m)) != hipSuccess) return e;
+    // MSM_RUN_NO_REDUCE: a later MSM takes these buckets into its reduction (bucket_slots); the slot's `done` event is not recorded
+    if (flags & MSM_RUN_NO_REDUCE) continue;
+    if ((e = msm_launch_reduction(*this, c, s, m)) != hipSuccess) return e;
   }
   return hipGetLastError();
 }

@@ -147,4 +147,98 @@ k_accum_g1_nc_w2(const AccumArgs<F, false> args, uint32_t total_buckets) {
   accum_g1_nc_body<F, 1, false, false>(args, total_buckets);
 }
 
+// TIMING ONLY (ZKMI_GATHER_MASK_BITS = k > 0): every table index of a sort is cut to its low k bits before the accumulation
+// reads it, so that all gathers hit a sub-table of 2^k entries that stays in L2.  The sums are WRONG by design: what is left
+// of a launch's time and held clock is the arithmetic alone, the bound of what any change to the fetch path can give.
+template <int UNUSED = 0>
+__global__ void k_mask_sorted(uint32_t* __restrict__ sorted, uint64_t n, uint32_t keep) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) sorted[i] &= keep;
+}
+
+// ---- what selects them: the A/B library's side of MsmEngine::run_device_multi (msm_impl.hpp) ----
+// In front of everything a call queues (all cap_entries words of the buffer: idempotent, and a sort may serve several MSMs).
+template <class F>
+static void msm_exp_mask_sorted(const MsmRunCall<F>& c, const MsmRunSchedule& s) {
+  if (s.exp_mask_bits <= 0 || s.exp_mask_bits >= 31) return;
+  for (int m = 0; m < c.nm; m++)
+    hipLaunchKernelGGL(k_mask_sorted<0>, dim3(1024), dim3(256), 0, c.st, c.sorts[m]->sorted, c.sorts[m]->cap_entries,
+                       0x80000000u | ((1u << s.exp_mask_bits) - 1u));
+}
+
+// The accumulation of MSM m (s.fused: of all MSMs of the call, m = 0) where a switch selects another launch than the
+// product's; false: the product's launch follows.
+//   ZKMI_ACCUM_G2 = 3: the G2 kernel at three waves; ZKMI_ACCUM / ZKMI_ACCUM_G2 = 0 | 1: the retired kernels above, in
+//   workgroups of ZKMI_ACCUM_BLOCK threads, every wave walking ZKMI_ACCUM_ROUNDS bucket groups; ZKMI_ACCUM = 2: two waves;
+//   ZKMI_QUAD* bit 4: a quad / octet per bucket (msm_quad.hpp k_accum_q: the complete law in line, no redo list) for plans of at
+//   most 2^16 buckets; bucket_slots without MSM_RUN_ADD_AT_REDUCE: the accumulate-INTO kernel; MSM_RUN_TWO_WAVES (the pipelined
+//   big MSM, msm_pipe.hpp: measured neutral) or ZKMI_ACCUM_W2 = 1: the occupancy-capped kernel.
+template <class F>
+static bool msm_exp_launch_accum(const MsmRunCall<F>& c, const MsmRunSchedule& s, int m) {
+  using K = MsmEngineKernels<F>;
+  using QPT = typename K::QPT;
+  const MsmSort& sort = *c.sorts[m];
+  const uint32_t tot_b = s.tot_b, heavy_thr = sort.plan.heavy_thr, block = s.exp_accum_block;
+  const hipStream_t st = c.st;
+  // grid of the retired kernels: one thread per bucket (G2: two), the waves striped over ZKMI_ACCUM_ROUNDS groups
+  auto striped = [&s, block](uint32_t threads) {
+    const uint32_t g = (threads + block - 1) / block, rounds = s.exp_accum_rounds > 1 ? s.exp_accum_rounds : 1;
+    return g ? (g + rounds - 1) / rounds : 1u;
+  };
+  // a quad / octet per bucket; blockIdx.y = the MSM of a fused launch (slots past nm repeat the first MSM)
+  auto launch_q = [&c, &s, m, tot_b, st] {
+    AccumQArgs<QPT> qa;
+    for (int k = 0; k < MSM_MULTI_MAX; k++) {
+      const int j = s.fused ? (k < c.nm ? k : 0) : m;
+      qa.bases[k] = c.bases[j];
+      qa.buckets[k] = c.bk[j];
+      qa.sort[k] = c.view(j);
+    }
+    hipLaunchKernelGGL(k_accum_q<QPT>, dim3((tot_b + QPT::PER_WAVE - 1) / QPT::PER_WAVE, s.fused ? c.nm : 1), dim3(64), 0, st, qa, tot_b);
+  };
+  if constexpr (K::LANES == 2) {
+    if (s.exp_accum_mode == 3)
+      hipLaunchKernelGGL((k_accum_g2_nc<3, 1>), dim3((2 * tot_b + 63) / 64), dim3(64), 0, st, c.bases[m], sort.begin, sort.count, sort.perm,
+                         sort.sorted, c.bk[m], tot_b, heavy_thr, c.redo[m]);
+    else if (s.exp_accum_mode != 2)
+      hipLaunchKernelGGL((block == 64 ? &k_accum_g2_split<1> : &k_accum_g2_split<4>), dim3(striped(2 * tot_b)), dim3(block), 0, st, c.bases[m],
+                         sort.begin, sort.count, sort.perm, sort.sorted, c.bk[m], tot_b, heavy_thr);
+    else if (s.exp_accum_q)
+      launch_q();
+    else
+      return false;
+  } else if (s.fused) {
+    if (s.exp_accum_q)
+      launch_q();
+    else if (s.accum != MSM_ACCUM_G1_SPLIT2 && s.exp_accum_mode != 3)
+      hipLaunchKernelGGL((k_accum_g1_nc<F, 2, 1, true>), dim3((tot_b + 63) / 64, c.nm), dim3(64), 0, st, c.fused_args(), tot_b);
+    else
+      return false;
+  } else {
+    const AccumArgs<F, false> one = {c.bases[m], c.bk[m], c.redo[m], c.view(m)};
+    if (c.into(m))
+      hipLaunchKernelGGL((k_accum_g1_nc<F, 3, 1, false, true>), dim3((tot_b + 63) / 64), dim3(64), 0, st, one, tot_b);
+    else if (s.exp_accum_mode == 2)
+      hipLaunchKernelGGL((k_accum_g1_nc<F, 2, 1>), dim3((tot_b + 63) / 64), dim3(64), 0, st, one, tot_b);
+    else if (s.exp_accum_mode == 1)
+      hipLaunchKernelGGL(k_accum<F>, dim3((tot_b + 255) / 256), dim3(256), 0, st, c.bases[m], sort.begin, sort.count, sort.perm, sort.sorted,
+                         c.bk[m], tot_b, heavy_thr);
+    else if (s.exp_accum_mode != 3)
+      hipLaunchKernelGGL((block == 64 ? &k_accum_g1_glds<F, 1> : &k_accum_g1_glds<F, 4>), dim3(striped(tot_b)), dim3(block), 0, st, c.bases[m],
+                         sort.begin, sort.count, sort.perm, sort.sorted, c.bk[m], tot_b, heavy_thr);
+    else if (s.exp_two_waves)
+      hipLaunchKernelGGL(k_accum_g1_nc_w2<F>, dim3((tot_b + 63) / 64), dim3(64), 0, st, one, tot_b);
+    else
+      return false;
+  }
+  return true;
+}
+
+// ZKMI_G2_TREE_SPLIT = 0: the unsliced G2 tree sum by the one-lane kernel (a lane per point: 330-register additions; the
+// schedule sizes the workgroup for it); true: *kernel is that kernel
+template <class F, class Kernel>
+static bool msm_exp_treesum_unsplit(const MsmRunSchedule& s, Kernel* kernel) {
+  if (s.exp_g2_tree_unsplit) *kernel = &k_treesum<F>;
+  return s.exp_g2_tree_unsplit;
+}
+
 }  // namespace zkmi

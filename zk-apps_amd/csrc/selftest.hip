@@ -167,3 +167,29 @@ extern "C" int32_t zkmi_selftest_host_pool(uint32_t callers, uint32_t jobs, uint
   return ZKMI_OK;
 }
 #endif  // ZKMI_TESTING
+
+// The launch schedule of the MSM driver (msm_impl.hpp msm_run_schedule) for one plan, engine and call shape, as numbers.
+#ifdef ZKMI_TESTING  // test scaffolding: libzkmi_exp.so only (include/zkmi_testing.h)
+#include "msm_impl.hpp"
+extern "C" int32_t zkmi_selftest_msm_run_schedule(uint64_t n, int32_t shared, uint64_t plan_n, int32_t engine, int32_t host_spin,
+                                                  int32_t nm, int32_t flags, int32_t* out, uint32_t n_out) {
+  if (!out || n == 0 || n > MSM_MAX_TERMS || plan_n > MSM_MAX_TERMS || (plan_n && shared) || engine < 0 || engine > 2 || nm < 1 ||
+      nm > MSM_MULTI_MAX)
+    return ZKMI_ERR_BAD_ARG;
+  MsmPlan pl = plan_n ? msm_make_plan_c(n, msm_make_plan(plan_n).c) : shared ? msm_make_plan_shared(n) : msm_make_plan(n);
+  const MsmRunSchedule s = msm_run_schedule(pl, (MsmEngineKind)engine, host_spin != 0, nm, flags, false);
+  pl.seg2_log = s.seg2_log;
+  const int32_t lanes = engine == MSM_ENGINE_G2 ? 2 : 1;
+  const int32_t v[] = {
+      pl.nwin, pl.c, (int32_t)s.tot_b, (int32_t)s.segs_per_win, (int32_t)s.tot_segs, s.seg, s.seg_bits, s.njobs, s.plain_job, s.t_job,
+      s.level2, (int32_t)s.segs2, (int32_t)s.tot_segs2, s.wide, s.quad_seg, s.quad_tree, s.quad_redo, s.quad_heavy,
+      (int32_t)s.nchunk, (int32_t)s.nq, (int32_t)s.tree_block, (int32_t)s.tree_lds, (int32_t)s.final_block, (int32_t)s.final_lds,
+      (int32_t)s.accum, s.fused, s.heavy_nc, MsmEngine<Fq28>::partials_per_msm(pl),
+      // what the buffers hold and the kernels assume
+      lanes, 2 * MSM_TREE_T / lanes, (int32_t)msm_quad_per_wave((MsmEngineKind)engine), MsmEngine<Fq28>::SLOT_PTS, (int32_t)MSM_STAGE_PTS_1, (int32_t)MSM_STAGE_PTS,
+      MSM_TREE_T, (int32_t)MSM_SEG2_MIN_SEGS, MSM_SEG2_LOG};
+  if (n_out != sizeof(v) / sizeof(v[0])) return ZKMI_ERR_BAD_ARG;
+  for (uint32_t i = 0; i < n_out; i++) out[i] = v[i];
+  return ZKMI_OK;
+}
+#endif  // ZKMI_TESTING

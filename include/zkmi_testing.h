@@ -60,7 +60,9 @@ int32_t zkmi_verify_each_kernel_ms(float out_ms[3]);
 int32_t zkmi_verify_batch_phases(double out_ms[7]);
 /* Device self-test of the quad-split complete addition (csrc/quad.hpp: one coordinate of an XYZZ point per lane of a quad)
  * against curve.hpp's one-lane addition on the device and the 32-bit-limb host arithmetic: n pairs with every special case
- * (o = a, o = -a, either at infinity, equal points in different representations), and 16-point sums over the quads of a wave. */
+ * (o = a, o = -a, either at infinity, equal points in different representations), and 16-point sums over the quads of a wave.
+ * Three instantiations, each with n pairs of its own: BLS12-381 G1 quads, G2 octets (8-point sums) and BN254 G1 quads
+ * (the 10-limb field of csrc/msm_bn.hip); out_mismatches is the total over the three. */
 int32_t zkmi_selftest_quad_add(zkmi_ctx* ctx, uint64_t seed, uint32_t n, uint32_t* out_mismatches);
 /* One operation of the device limb arithmetic (csrc/field28.hpp) on n tuples of RAW limb arrays: every operand and every
  * result is NL int32 limbs (14 for field 0, 10 for the others), tuple after tuple, and nothing is converted on the way in or

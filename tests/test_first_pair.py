@@ -54,8 +54,9 @@ def plan_of(zk, n, shared):
     return {"c": c, "nd": nd, "buckets": parts * nb, "shared": shared}
 
 
-def design(n, plan):
-    """n terms [(point id or None, negated, scalar)] and the number of distinct points they use."""
+def design(n, plan, r=R):
+    """n terms [(point id or None, negated, scalar)] and the number of distinct points they use; r: the scalar field's modulus
+    (the designed scalars are below 2^250, so the terms are the same for every curve whose r is above that)."""
     c, nd, shared = plan["c"], plan["nd"], plan["shared"]
     h = 1 << (c - 1)
     wmax = nd - 2  # positions 0 .. wmax - 1: the carry of a negative digit stays below the top digit
@@ -69,7 +70,7 @@ def design(n, plan):
 
     def scalar(w, m, neg):
         s = (1 << (c * (w + 1))) - (m << (c * w)) if neg else m << (c * w)
-        assert 0 < s < R
+        assert 0 < s < r
         return s
 
     while len(terms) < n:
@@ -119,13 +120,14 @@ def census(terms, plan):
     return out
 
 
-def materialise(terms, points, width):
-    """Wire bytes of bases and scalars; points = wire bytes of the distinct points, width = 96 (G1) | 192 (G2)."""
+def materialise(terms, points, width, p=P, comp=48):
+    """Wire bytes of bases and scalars; points = wire bytes of the distinct points, width = 96 (G1) | 192 (G2) with the
+    defaults, 64 with p = BN254's base field modulus and comp = 32 bytes per field component."""
     half = width // 2
 
-    def neg(pt):  # y -> p - y per 48-byte component
-        ys = [(P - int.from_bytes(pt[half + 48 * i : half + 48 * i + 48], "little")) % P for i in range(half // 48)]
-        return pt[:half] + b"".join(y.to_bytes(48, "little") for y in ys)
+    def neg(pt):  # y -> p - y per component
+        ys = [(p - int.from_bytes(pt[half + comp * i : half + comp * i + comp], "little")) % p for i in range(half // comp)]
+        return pt[:half] + b"".join(y.to_bytes(comp, "little") for y in ys)
 
     bases, scalars = [], []
     for pid, negated, s in terms:

@@ -1106,7 +1106,12 @@ def test_poseidon_and_bn254_golden_fixtures_on_gpu(ctx, zk):
 
 def test_bn254_prepared_srs_matches_plain_msm(ctx):
     """zkmi_bn254_srs_prepare (fixed-base table, shared buckets) gives the same MSM / commitment as the
-    windowed schedule, for small, odd and large lengths and for edge scalars."""
+    windowed schedule, for small, odd and large lengths and for edge scalars.
+
+    Above 77 terms this compares the prepared path with the plain one only: both run the same kernels, so an error they
+    share passes here.  The prepared path meets an independent reference (the sum of discrete logs, bn254_msm_cases.py) in
+    test_gpu_bn254_msm.py: designed first-pair inputs at 4 000 terms, heavy buckets at 2 561 ... 2 625 and 54 000, witness-like
+    scalars at 5 000 and 70 000, every irregular size up to 4 097, and both sides of the second-level threshold."""
     import torch
     from oracle import bn254 as bn
 
@@ -2129,7 +2134,8 @@ def test_quad_split_addition_selftest(ctx, zk):
     pass and heavy-bucket sums of the G1 MSM run on it: csrc/msm_quad.hpp) -- against curve.hpp's one-lane addition on the
     device and the host's 32-bit-limb arithmetic: 4 096 pairs with every special case (o = a and o = -a in the same and in
     another representation, either operand at infinity, both), and 16-point sums over the quads of a wave from XYZZ and
-    from affine sources (signs, entries at infinity, a doubling and a cancellation inside the tree)."""
+    from affine sources (signs, entries at infinity, a doubling and a cancellation inside the tree).  Three instantiations,
+    4 096 pairs each: BLS12-381 G1 quads, G2 octets, and the quads of the 10-limb BN254 field (csrc/msm_bn.hip)."""
     import ctypes as C
 
     bad = C.c_uint32(99)

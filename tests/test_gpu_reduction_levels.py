@@ -47,10 +47,12 @@ def sizes_around_the_threshold(zk):
     return {"below": 1 << max(below), "above": 1 << min(above), "sliced": sliced}
 
 
-def scalars(zk, kind, n, seed):
+def scalars(zk, kind, n, seed, r=R, top_mask=0x3F):
+    """32-byte scalars below r; top_mask keeps the uniform draws below it (0x3F: 2^254 < BLS12-381's r, the default)"""
+    assert (top_mask + 1) << 248 <= r
     rng = np.random.default_rng(seed)
     a = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
-    a[:, 31] &= 0x3F
+    a[:, 31] &= top_mask
     if kind == "ones":  # only the bucket of weight 1 is loaded: every other term of the running sums is infinity
         a[:] = 0
         a[:, 0] = 1
@@ -60,7 +62,7 @@ def scalars(zk, kind, n, seed):
         c, nd = zk.msm_plan_query(n, shared=True)[:2]
         k = 0
         for w in range(nd):
-            if k + (1 << (c * w + c - 1)) < R:
+            if k + (1 << (c * w + c - 1)) < r:
                 k += 1 << (c * w + c - 1)
         a[:] = np.frombuffer(k.to_bytes(32, "little"), dtype=np.uint8)
     elif kind == "witness_like":  # bench.py's mix: 40 % zero, 20 % one, 10 % below 2^16, 30 % uniform

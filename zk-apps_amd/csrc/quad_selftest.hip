@@ -1,5 +1,5 @@
-// zkmi — device self-test of the quad-split (G1) and octet-split (G2) group law (quad.hpp) against the one-lane XYZZ::add of
-// curve.hpp.  TEST SCAFFOLDING (include/zkmi_testing.h): compiled into libzkmi_exp.so only.
+// zkmi — device self-test of the quad-split (G1, BN254 G1) and octet-split (G2) group law (quad.hpp) against the one-lane
+// XYZZ::add of curve.hpp.  TEST SCAFFOLDING (include/zkmi_testing.h): compiled into libzkmi_exp.so only.
 #include "ctx.hpp"
 #include "quad.hpp"
 #include <stdio.h>
@@ -17,28 +17,41 @@ struct Rng {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
   }
-  Fq fq() {
-    // uniform over [0, p) up to the bias of the top word's reduction: the top word modulo its largest value + 1, and a
-    // draw that still is >= p (top word equal to p's, the rest not below) is rejected
+  template <class P>
+  Fp<P> fq() {
+    // uniform over [0, p) of the field P up to the bias of the top word's reduction: the top word modulo its largest
+    // value + 1, and a draw that still is >= p (top word equal to p's, the rest not below) is rejected
+    constexpr int N = P::N;
     for (;;) {
-      Fq a;
-      for (int i = 0; i < 12; i += 2) {
+      Fp<P> a;
+      for (int i = 0; i < N; i += 2) {
         uint64_t v = next();
         a.l[i] = (uint32_t)v;
         a.l[i + 1] = (uint32_t)(v >> 32);
       }
-      a.l[11] %= FqParams::MOD[11] + 1u;
+      a.l[N - 1] %= P::MOD[N - 1] + 1u;
       bool below = false;
-      for (int i = 11; i >= 0; i--)
-        if (a.l[i] != FqParams::MOD[i]) {
-          below = a.l[i] < FqParams::MOD[i];
+      for (int i = N - 1; i >= 0; i--)
+        if (a.l[i] != P::MOD[i]) {
+          below = a.l[i] < P::MOD[i];
           break;
         }
       if (below) return a;  // arbitrary residue, read as Montgomery form
     }
   }
-  void draw(Fq& x) { x = fq(); }
-  void draw(Fq2& x) { x = {fq(), fq()}; }
+  template <class P>
+  void draw(Fp<P>& x) { x = fq<P>(); }
+  void draw(Fq2& x) { x = {fq<FqParams>(), fq<FqParams>()}; }
+};
+
+// the base field of a device coordinate type: itself, or the component type of a quadratic extension
+template <class DF>
+struct BaseOf {
+  using T = DF;
+};
+template <class B>
+struct BaseOf<Fq2T<B>> {
+  using T = B;
 };
 
 template <class DF>
@@ -50,7 +63,7 @@ __global__ void k_add_one_lane(const XYZZ<DF>* a, const XYZZ<DF>* o, XYZZ<DF>* o
   out[i] = r;
 }
 template <class PT, bool DBG>
-__global__ void __launch_bounds__(64, 2) k_add_quad(const typename PT::Point* a, const typename PT::Point* o, typename PT::Point* out, uint32_t n, Fq28* dbg) {
+__global__ void __launch_bounds__(64, 2) k_add_quad(const typename PT::Point* a, const typename PT::Point* o, typename PT::Point* out, uint32_t n, decltype(PT::v)* dbg) {
   const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) / PT::LANES;
   if (i >= n) return;
   PT r = PT::load(a + i);
@@ -82,8 +95,9 @@ bool same(const XYZZ<DF>& d, const XYZZ<HF>& h) {
 // device and by the 32-bit-limb host arithmetic; plus sums over the points of a wave (XYZZ and affine sources).
 template <class HF, class DF, bool EXT2>
 int32_t run(zkmi_ctx* ctx, uint64_t seed, uint32_t n, uint32_t* out_bad, const char* name) {
-  using PT = XYZZQ<Fq28, 0, EXT2>;
-  using PTB = XYZZQ<Fq28, 1, EXT2>;
+  using BF = typename BaseOf<DF>::T;
+  using PT = XYZZQ<BF, 0, EXT2>;
+  using PTB = XYZZQ<BF, 1, EXT2>;
   constexpr uint32_t PW = PT::PER_WAVE;
   Rng rng{seed};
   std::vector<XYZZ<HF>> ha(n), ho(n);
@@ -140,8 +154,8 @@ int32_t run(zkmi_ctx* ctx, uint64_t seed, uint32_t n, uint32_t* out_bad, const c
     goto out;
   }
   hipLaunchKernelGGL(k_add_one_lane<DF>, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, ga, go, g1, n);
-  hipLaunchKernelGGL((k_add_quad<PT, false>), dim3((PT::LANES * n + 63) / 64), dim3(64), 0, ctx->stream, ga, go, gq, n, (Fq28*)nullptr);
-  hipLaunchKernelGGL((k_add_quad<PTB, false>), dim3((PT::LANES * n + 63) / 64), dim3(64), 0, ctx->stream, ga, go, gb, n, (Fq28*)nullptr);
+  hipLaunchKernelGGL((k_add_quad<PT, false>), dim3((PT::LANES * n + 63) / 64), dim3(64), 0, ctx->stream, ga, go, gq, n, (BF*)nullptr);
+  hipLaunchKernelGGL((k_add_quad<PTB, false>), dim3((PT::LANES * n + 63) / 64), dim3(64), 0, ctx->stream, ga, go, gb, n, (BF*)nullptr);
   hipLaunchKernelGGL(k_wave_sum<PT>, dim3(n / PW), dim3(64), 0, ctx->stream, ga, gaff, gs);
   if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(r1.data(), g1, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(rq.data(), gq, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(rb.data(), gb, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -210,6 +224,8 @@ extern "C" int32_t zkmi_selftest_quad_add(zkmi_ctx* ctx, uint64_t seed, uint32_t
   *out_mismatches = 0;
   int32_t rc = run<Fq, Fq28, false>(ctx, seed, n, out_mismatches, "G1 quads");
   if (rc != ZKMI_OK) return rc;
-  return run<Fq2, Fq2_28, true>(ctx, seed + 1, n, out_mismatches, "G2 octets");
+  rc = run<Fq2, Fq2_28, true>(ctx, seed + 1, n, out_mismatches, "G2 octets");
+  if (rc != ZKMI_OK) return rc;
+  return run<BnFq, BnFq28, false>(ctx, seed + 2, n, out_mismatches, "BN254 quads");
 }
 #endif  // ZKMI_TESTING

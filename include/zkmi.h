@@ -675,6 +675,47 @@ int32_t zkmi_srs_verify(zkmi_ctx* ctx, const zkmi_srs* srs, const uint8_t seed[3
 int32_t zkmi_pk_verify_contribution(zkmi_ctx* ctx, const zkmi_pk* before, const zkmi_pk* after, const uint8_t seed[32],
                                     uint32_t* out_failed);
 
+/* ---- phase-1 contributions: every point of an array times a scalar of its own ---------------------------------- *
+ * out[i] = k[i] * P[i].  P: n points in HBM, affine WIRE form; k: n x 32 B little-endian canonical (< r) in HBM; both
+ * 4-byte aligned, as d_out is; d_out may equal d_points.  Infinity in, infinity out; k[i] = 0 gives infinity.  The points
+ * must be in the r-order subgroup (caller's duty).  A NULL argument or n = 0: ZKMI_ERR_BAD_ARG; a coordinate >= p or a
+ * scalar >= r: ZKMI_ERR_NON_CANONICAL, nothing written.  One lane per point, a fixed signed 4-bit window: every lane of a
+ * wave runs the same sequence of group operations whatever its scalar.  Waits for the result. */
+int32_t zkmi_g1_points_mul_each_dev(zkmi_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, void* d_out);
+int32_t zkmi_g2_points_mul_each_dev(zkmi_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, void* d_out);
+/* P[i] <- (c * q^i) * P[i] in place, the scalars made on the device; c, q: 32 B canonical, < r (host memory).  Otherwise
+ * as above.  The library overwrites its copies of c, q and of every power before it frees them. */
+int32_t zkmi_g1_points_mul_powers_dev(zkmi_ctx* ctx, void* d_points, uint64_t n, const uint8_t c[32], const uint8_t q[32]);
+int32_t zkmi_g2_points_mul_powers_dev(zkmi_ctx* ctx, void* d_points, uint64_t n, const uint8_t c[32], const uint8_t q[32]);
+/* One phase-1 contribution sab = s | a | b (3 x 32 B canonical, each 0 < . < r), on an idle resident transcript:
+ *   tau_g1[i] <- s^i tau_g1[i], tau_g2[i] <- s^i tau_g2[i], alpha_tau_g1[i] <- a s^i (.), beta_tau_g1[i] <- b s^i (.),
+ *   beta_g2 <- b beta_g2.   out_step_g2 = [s]G2 | [a]G2 | [b]G2 (3 x 192 B wire): what a verifier needs.
+ * Waits for everything queued on the context first.  The new arrays are written beside the old ones and swapped in at
+ * the end: a refused or failed call leaves the transcript byte for byte as it was; `checks` is kept.  A zero scalar or a
+ * NULL argument: ZKMI_ERR_BAD_ARG; a scalar >= r: ZKMI_ERR_NON_CANONICAL.
+ * s, a and b are toxic waste: every host and device copy the call makes of them or of their powers is overwritten
+ * with zeros before it is freed.  The caller's sab is the caller's to destroy. */
+int32_t zkmi_srs_contribute(zkmi_ctx* ctx, zkmi_srs* srs, const uint8_t sab[96], uint8_t out_step_g2[576]);
+/* `after` is `before` moved by one contribution whose step elements are step_g2 = [s]G2 | [a]G2 | [b]G2 (a verifier chains
+ * calls).  *out_failed: the ZKMI_SRS_* mask of `after` in the low six bits, exactly as zkmi_srs_verify(after, seed) reports
+ * it, and on top: */
+#define ZKMI_SRS_STEP_BAD_TAU     256u  /* e(after.tau_g1[1], G2)       != e(before.tau_g1[1], step_s) */
+#define ZKMI_SRS_STEP_BAD_ALPHA   512u  /* e(after.alpha_tau_g1[0], G2) != e(before.alpha_tau_g1[0], step_a) */
+#define ZKMI_SRS_STEP_BAD_BETA   1024u  /* the same for beta_tau_g1[0] and step_b */
+#define ZKMI_SRS_STEP_DEGENERATE 2048u  /* a step element, or an anchor of `before` that a step is compared on, is infinity */
+/* The step equations share the Miller-loop and final-exponentiation launches of the consistency equations; each is its own
+ * two-pair product.  STEP_DEGENERATE is reported without the step equations, ZKMI_SRS_DEGENERATE without the consistency
+ * ones.  A transcript with no tau_g1[1] (the domain of size 1) has no tau step to compare: STEP_BAD_TAU is not raised.
+ * The step elements are parsed and subgroup-checked on the host: a bad one is ZKMI_ERR_NON_CANONICAL.  ZKMI_ERR_BAD_ARG:
+ * NULLs, different shapes, a transcript of another context or device, or one not loaded under ZKMI_CHECK_SUBGROUP.
+ * ZKMI_OK with *out_failed = 0, or ZKMI_ERR_VERIFICATION with the mask.  seed NULL: drawn from the OS.
+ * What this proves: given a `before` that verifies, `after` is `before` moved by the discrete logarithms of the step
+ * elements.  What it does NOT prove: that anybody knows those logarithms.  Proofs of knowledge of s, a and b, and the
+ * hash of the transcript they are bound to, are the coordinator's protocol and the caller's to check, as the verifying
+ * key's bytes are the caller's to patch. */
+int32_t zkmi_srs_verify_contribution(zkmi_ctx* ctx, const zkmi_srs* before, const zkmi_srs* after, const uint8_t step_g2[576],
+                                     const uint8_t seed[32], uint32_t* out_failed);
+
 /* ---- row a12: the reference's prove/verify surface ------------------------ */
 #define ZKMI_MERKLE_TREE_DEPTH 10 /* shielder/mocked_zk/src/lib.rs:16 */
 #define ZKMI_TOKENS_NUMBER 2      /* shielder/mocked_zk/src/lib.rs:17 */

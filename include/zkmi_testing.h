@@ -199,6 +199,24 @@ int32_t zkmi_selftest_rlc_weights_host(const uint8_t seed[32], uint32_t dom, uin
  * wait): [0] weights, [1] conversion to the MSM's base form, [2] MSMs, [3] pairing products.  One global, last call wins;
  * the product library records nothing. */
 int32_t zkmi_ceremony_phases(double out_ms[4]);
+/* points_mul.hip: out[i] = k[i] * P[i] through the per-point body the multiplication kernel runs (the signed 4-bit window
+ * and the lane's table of multiples), in a host loop.  group 1 | 2; wire_points n x 96 / 192 B affine WIRE form, scalars
+ * n x 32 B canonical, out_wire as wire_points.  A coordinate >= p or a scalar >= r: ZKMI_ERR_NON_CANONICAL. */
+int32_t zkmi_selftest_points_mul_each_host(int32_t group, const uint8_t* wire_points, const uint8_t* scalars, uint64_t n,
+                                           uint8_t* out_wire);
+/* c * q^i for i = first .. first + count - 1 through the body the powers kernel runs, in a host loop that cuts the range at
+ * the multiples of the chunk a lane walks: out = count x 32 B canonical.  first + count <= 2^40.  The second call returns
+ * that chunk size and the window width of the multiplication body (bits), for tests that place their cases around them. */
+int32_t zkmi_selftest_fr_powers_host(const uint8_t c[32], const uint8_t q[32], uint64_t first, uint64_t count, uint8_t* out);
+int32_t zkmi_selftest_points_mul_shape(uint32_t* out_chunk, uint32_t* out_window);
+/* Which multiplication kernel the calls of THIS library launch from now on: 0 the windowed one (the product's), 1 the plain
+ * one (one lane per point around the bit-by-bit double-and-add: the yardstick, not in the product library), -1 back to what
+ * ZKMI_POINTS_MUL_PLAIN said when the library first looked. */
+int32_t zkmi_points_mul_kernel(int32_t which);
+/* The multiplications of this library since the last contribution began (or since the last call of this function with
+ * reset != 0), in ms of host clock, every phase ending in a stream wait: [0] powers, [1] G1 multiplication kernels, [2] G2
+ * multiplication kernels, [3] affine stores, conversions and allocation.  The product library records nothing. */
+int32_t zkmi_points_mul_phases(double out_ms[4], int32_t reset);
 
 #ifdef __cplusplus
 }

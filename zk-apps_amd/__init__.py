@@ -30,6 +30,10 @@ from .binding import (  # noqa: F401
     SRS_BAD_BETA,
     SRS_BAD_BETA_G2,
     SRS_DEGENERATE,
+    SRS_STEP_BAD_TAU,
+    SRS_STEP_BAD_ALPHA,
+    SRS_STEP_BAD_BETA,
+    SRS_STEP_DEGENERATE,
     PK2_FIXED_PART_DIFFERS,
     PK2_BAD_DELTA,
     PK2_BAD_H,

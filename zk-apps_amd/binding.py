@@ -38,6 +38,8 @@ NO_INDEX = (1 << 64) - 1
 # masks of Context.srs_verify / Context.pk_verify_contribution (include/zkmi.h)
 SRS_BAD_TAU_G1, SRS_BAD_TAU_G2, SRS_BAD_ALPHA, SRS_BAD_BETA, SRS_BAD_BETA_G2, SRS_DEGENERATE = 1, 2, 4, 8, 16, 32
 PK2_FIXED_PART_DIFFERS, PK2_BAD_DELTA, PK2_BAD_H, PK2_BAD_L = 1, 2, 4, 8
+# on top of the SRS_* mask of `after`: Context.srs_verify_contribution
+SRS_STEP_BAD_TAU, SRS_STEP_BAD_ALPHA, SRS_STEP_BAD_BETA, SRS_STEP_DEGENERATE = 256, 512, 1024, 2048
 MERKLE_TREE_DEPTH = 10
 MAX_TREE_HEIGHT = 32
 TOKENS_NUMBER = 2
@@ -562,6 +564,40 @@ class Zkmi:
         out = (C.c_uint8 * (16 * max(1, count)))()
         self._chk(self.tlib.zkmi_selftest_rlc_weights_host(_buf(seed), C.c_uint32(dom), C.c_uint64(first), C.c_uint64(count), out))
         return bytes(out)[: 16 * count]
+
+    def selftest_points_mul_each_host(self, group, wire_points, scalars):
+        """Testing library: out[i] = k[i] * P[i] through the per-point body k_points_mul runs, in a host loop -> wire bytes."""
+        w = 96 if group == 1 else 192
+        n = len(scalars) // 32
+        assert len(wire_points) == w * n and len(scalars) == 32 * n
+        out = (C.c_uint8 * (w * max(1, n)))()
+        self._chk(self.tlib.zkmi_selftest_points_mul_each_host(C.c_int32(group), _buf(wire_points), _buf(scalars), C.c_uint64(n), out))
+        return bytes(out)[: w * n]
+
+    def selftest_fr_powers_host(self, c, q, first, count):
+        """Testing library: c * q^i for i in [first, first + count) through the body k_fr_powers runs, in a host loop cut at
+        the chunk boundaries -> count x 32 bytes (canonical scalars)."""
+        assert len(c) == 32 and len(q) == 32
+        out = (C.c_uint8 * (32 * max(1, count)))()
+        self._chk(self.tlib.zkmi_selftest_fr_powers_host(_buf(c), _buf(q), C.c_uint64(first), C.c_uint64(count), out))
+        return bytes(out)[: 32 * count]
+
+    def selftest_points_mul_shape(self):
+        """Testing library: (indices a lane of k_fr_powers walks, window width of the multiplication body in bits)."""
+        chunk, window = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self.tlib.zkmi_selftest_points_mul_shape(C.byref(chunk), C.byref(window)))
+        return int(chunk.value), int(window.value)
+
+    def points_mul_kernel(self, which):
+        """Testing library: the multiplication kernel ITS calls launch from now on: 0 windowed, 1 plain, -1 as the environment said."""
+        self._chk(self.tlib.zkmi_points_mul_kernel(C.c_int32(which)))
+
+    def points_mul_phases(self, reset=False):
+        """Testing library: ms of its multiplications since the last contribution began (powers, G1 kernels, G2 kernels, stores
+        and allocation)."""
+        out = (C.c_double * 4)()
+        self._chk(self.tlib.zkmi_points_mul_phases(out, C.c_int32(int(reset))))
+        return tuple(out)
 
     # ---- reference prove/verify surface (mocked_zk mirror) -------------------
     def account_new(self, tokens):
@@ -1095,6 +1131,36 @@ class Context:
                      C.c_uint32(dom), lo, hi))
         return bytes(lo), bytes(hi)
 
+    def points_mul_each_dev(self, group, d_points, d_scalars, n, d_out):
+        """zkmi_g{1,2}_points_mul_each_dev: out[i] = k[i] * P[i] for n subgroup points (affine wire form) and n canonical
+        32-byte scalars at device addresses; d_out may equal d_points."""
+        fn = self.lib.zkmi_g1_points_mul_each_dev if group == 1 else self.lib.zkmi_g2_points_mul_each_dev
+        ptr = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        self._chk(fn(self.h, ptr(d_points), ptr(d_scalars), C.c_uint64(n), ptr(d_out)))
+
+    def points_mul_powers_dev(self, group, d_points, n, c, q):
+        """zkmi_g{1,2}_points_mul_powers_dev: P[i] <- (c q^i) P[i] in place, the scalars made on the device (c, q: 32 bytes
+        canonical)."""
+        fn = self.lib.zkmi_g1_points_mul_powers_dev if group == 1 else self.lib.zkmi_g2_points_mul_powers_dev
+        self._chk(fn(self.h, C.c_void_p(d_points) if d_points else None, C.c_uint64(n), _buf(c) if c is not None else None,
+                     _buf(q) if q is not None else None))
+
+    def srs_contribute(self, srs, sab):
+        """zkmi_srs_contribute: one phase-1 contribution s | a | b (96 bytes canonical, each non-zero) in place ->
+        step_g2 = [s]G2 | [a]G2 | [b]G2 (576 bytes), what srs_verify_contribution takes."""
+        step = (C.c_uint8 * 576)()
+        self._chk(self.lib.zkmi_srs_contribute(self.h, srs.h, _buf(sab) if sab is not None else None, step))
+        return bytes(step)
+
+    def srs_verify_contribution(self, before, after, step_g2, seed=None):
+        """zkmi_srs_verify_contribution: `after` is `before` moved by the contribution whose step elements are step_g2 ->
+        (ok, failed_mask: the SRS_* mask of `after` plus SRS_STEP_*).  It does not prove that anybody knows s, a, b."""
+        assert seed is None or len(seed) == 32
+        failed = C.c_uint32(0)
+        rc = self.lib.zkmi_srs_verify_contribution(self.h, before.h, after.h, _buf(step_g2) if step_g2 is not None else None,
+                                                   _buf(seed) if seed is not None else None, C.byref(failed))
+        return self._verdict(rc, failed)
+
     def ceremony_phases(self):
         """Testing library: ms of the last srs_verify / pk_verify_contribution made through it (weights, conversion, MSMs,
         pairing products)."""
@@ -1280,6 +1346,14 @@ class Srs:
     def verify(self, seed=None):
         """zkmi_srs_verify -> (ok, failed_mask)."""
         return self.ctx.srs_verify(self, seed)
+
+    def contribute(self, sab):
+        """zkmi_srs_contribute in place -> step_g2 (576 bytes)."""
+        return self.ctx.srs_contribute(self, sab)
+
+    def verify_contribution(self, before, step_g2, seed=None):
+        """zkmi_srs_verify_contribution of this transcript against its predecessor `before` -> (ok, failed_mask)."""
+        return self.ctx.srs_verify_contribution(before, self, step_g2, seed)
 
     def free(self):
         if self.h:

@@ -1,6 +1,8 @@
 // zkmi — verifying what a ceremony hands over: the same-ratio checks of a phase-1 transcript
-// (zkmi_srs_verify) and of a phase-2 contribution (zkmi_pk_verify_contribution), and the layer below them, the weighted
-// sums of a point array and of the array shifted by one (zkmi_g{1,2}_points_adjacent_sums_dev).
+// (zkmi_srs_verify), of a phase-1 contribution (zkmi_srs_verify_contribution: the same checks of the new transcript plus one
+// step equation per contributed scalar) and of a phase-2 contribution (zkmi_pk_verify_contribution), and the
+// layer below them, the weighted sums of a point array and of the array shifted by one
+// (zkmi_g{1,2}_points_adjacent_sums_dev).
 //
 // A chain P_0, P_1, ... has one ratio tau iff e(P_{i+1}, G2) = e(P_i, [tau]G2) for every i.  The m - 1 equations are taken
 // as ONE random linear combination: with lo = sum w_i P_i and hi = sum w_i P_{i+1}, e(hi, G2) = e(lo, [tau]G2).  The weights
@@ -275,6 +277,69 @@ int32_t draw_seed(zkmi_ctx* ctx, const uint8_t* seed, uint8_t drawn[32], const u
   return ZKMI_OK;
 }
 
+// the points the equations of a transcript are anchored on (infinity where the transcript has no such entry)
+struct SrsAnchors {
+  G1Affine tau1 = G1Affine::infinity(), alpha0 = G1Affine::infinity(), beta0 = G1Affine::infinity();
+  G2Affine tau2 = G2Affine::infinity();
+};
+
+int32_t srs_anchors(zkmi_ctx* ctx, const zkmi_srs* srs, SrsAnchors* a) {
+  if (srs->n_tau_g1 > 1) ZK_HIP(ctx, hipMemcpy(&a->tau1, srs->tau_g1 + 1, sizeof(G1Affine), hipMemcpyDeviceToHost));
+  if (srs->n_tau_g2 > 1) ZK_HIP(ctx, hipMemcpy(&a->tau2, srs->tau_g2 + 1, sizeof(G2Affine), hipMemcpyDeviceToHost));
+  ZK_HIP(ctx, hipMemcpy(&a->alpha0, srs->alpha_tau_g1, sizeof(G1Affine), hipMemcpyDeviceToHost));
+  ZK_HIP(ctx, hipMemcpy(&a->beta0, srs->beta_tau_g1, sizeof(G1Affine), hipMemcpyDeviceToHost));
+  return ZKMI_OK;
+}
+
+// a transcript the checks may be run on: of this context and device, every point read under ZKMI_CHECK_SUBGROUP
+int32_t srs_verifiable(zkmi_ctx* ctx, const zkmi_srs* srs) {
+  if (srs->ctx != ctx || srs->device != ctx->device) return ctx->fail(ZKMI_ERR_BAD_ARG, "transcript of another context");
+  if (!(srs->checks & ZKMI_CHECK_SUBGROUP))
+    return ctx->fail(ZKMI_ERR_BAD_ARG, "transcript was loaded without ZKMI_CHECK_SUBGROUP: its sums prove nothing");
+  return ZKMI_OK;
+}
+
+// The five same-ratio equations of a resident transcript, appended to *eqs for the caller's one launch of pairings; a
+// degenerate transcript raises ZKMI_SRS_DEGENERATE in *failed and appends nothing.  *an: the anchors that were read.
+int32_t srs_consistency(zkmi_ctx* ctx, const zkmi_srs* srs, const uint8_t* seed, SrsAnchors* an, uint32_t* failed,
+                        std::vector<PairEq>* eqs) {
+  int32_t rc = srs_anchors(ctx, srs, an);
+  if (rc != ZKMI_OK) return rc;
+  const bool has_tau = srs->n_tau_g1 > 1 || srs->n_tau_g2 > 1 || srs->n_ab > 1;  // any power of tau above tau^0
+  const G1Affine &tau1 = an->tau1, &alpha0 = an->alpha0, &beta0 = an->beta0;
+  const G2Affine& tau2 = an->tau2;
+  if ((has_tau && (tau1.is_inf() || tau2.is_inf())) || alpha0.is_inf() || beta0.is_inf() || srs->beta_g2.is_inf()) {
+    *failed |= ZKMI_SRS_DEGENERATE;
+    return ZKMI_OK;
+  }
+  if (has_tau) {
+    // the three G1 chains against [tau]G2:  e(hi, G2) e(-lo, tau_g2[1]) = 1
+    struct {
+      const G1Affine* chain;
+      uint64_t m;
+      uint32_t dom, bit;
+    } const chains[3] = {{srs->tau_g1, srs->n_tau_g1, 0, ZKMI_SRS_BAD_TAU_G1},
+                         {srs->alpha_tau_g1, srs->n_ab, 2, ZKMI_SRS_BAD_ALPHA},
+                         {srs->beta_tau_g1, srs->n_ab, 3, ZKMI_SRS_BAD_BETA}};
+    for (const auto& c : chains) {
+      uint8_t lo_w[96], hi_w[96];
+      if ((rc = weighted_sums<1>(ctx, c.chain, nullptr, c.m, seed, c.dom, true, lo_w, hi_w)) != ZKMI_OK) return rc;
+      G1Affine lo, hi;
+      if (!wire_g1(lo_w, &lo) || !wire_g1(hi_w, &hi)) return ctx->fail(ZKMI_ERR_HIP, "ceremony: the MSM returned a non-canonical point");
+      eqs->push_back({hi, g2_generator(), lo.neg(), tau2, c.bit});
+    }
+    // the G2 chain against [tau]G1:  e(tau_g1[1], lo) e(-G1, hi) = 1; its term i = 0 ties tau in G1 to tau in G2
+    uint8_t lo_w[192], hi_w[192];
+    if ((rc = weighted_sums<2>(ctx, srs->tau_g2, nullptr, srs->n_tau_g2, seed, 1, true, lo_w, hi_w)) != ZKMI_OK) return rc;
+    G2Affine lo, hi;
+    if (!wire_g2(lo_w, &lo) || !wire_g2(hi_w, &hi)) return ctx->fail(ZKMI_ERR_HIP, "ceremony: the MSM returned a non-canonical point");
+    eqs->push_back({tau1, lo, g1_generator().neg(), hi, ZKMI_SRS_BAD_TAU_G2});
+  }
+  // beta in G1 and in G2:  e(beta_tau_g1[0], G2) e(-G1, beta_g2) = 1
+  eqs->push_back({beta0, g2_generator(), g1_generator().neg(), srs->beta_g2, ZKMI_SRS_BAD_BETA_G2});
+  return ZKMI_OK;
+}
+
 }  // namespace
 
 int32_t pk_verify_contribution(zkmi_ctx* ctx, const PkCeremonyView& before, const PkCeremonyView& after, const uint8_t seed_in[32],
@@ -355,57 +420,79 @@ int32_t zkmi_srs_verify(zkmi_ctx* ctx, const zkmi_srs* srs, const uint8_t seed_i
   ZK_ENTER(ctx);
   if (!srs || !out_failed) return ZKMI_ERR_BAD_ARG;
   *out_failed = 0;
-  if (srs->ctx != ctx || srs->device != ctx->device) return ctx->fail(ZKMI_ERR_BAD_ARG, "transcript of another context");
-  if (!(srs->checks & ZKMI_CHECK_SUBGROUP))
-    return ctx->fail(ZKMI_ERR_BAD_ARG, "transcript was loaded without ZKMI_CHECK_SUBGROUP: its sums prove nothing");
+  int32_t rc = srs_verifiable(ctx, srs);
+  if (rc != ZKMI_OK) return rc;
   uint8_t drawn[32];
   const uint8_t* seed = nullptr;
-  int32_t rc = draw_seed(ctx, seed_in, drawn, &seed);
-  if (rc != ZKMI_OK) return rc;
+  if ((rc = draw_seed(ctx, seed_in, drawn, &seed)) != ZKMI_OK) return rc;
   ZK_HIP(ctx, ctx->drain());
   phases_reset();
-  // the five points the equations are anchored on
-  const bool has_tau = srs->n_tau_g1 > 1 || srs->n_tau_g2 > 1 || srs->n_ab > 1;  // any power of tau above tau^0
-  G1Affine tau1 = G1Affine::infinity(), alpha0, beta0;
-  G2Affine tau2 = G2Affine::infinity();
-  if (srs->n_tau_g1 > 1) ZK_HIP(ctx, hipMemcpy(&tau1, srs->tau_g1 + 1, sizeof(G1Affine), hipMemcpyDeviceToHost));
-  if (srs->n_tau_g2 > 1) ZK_HIP(ctx, hipMemcpy(&tau2, srs->tau_g2 + 1, sizeof(G2Affine), hipMemcpyDeviceToHost));
-  ZK_HIP(ctx, hipMemcpy(&alpha0, srs->alpha_tau_g1, sizeof(G1Affine), hipMemcpyDeviceToHost));
-  ZK_HIP(ctx, hipMemcpy(&beta0, srs->beta_tau_g1, sizeof(G1Affine), hipMemcpyDeviceToHost));
-  if ((has_tau && (tau1.is_inf() || tau2.is_inf())) || alpha0.is_inf() || beta0.is_inf() || srs->beta_g2.is_inf()) {
-    *out_failed = ZKMI_SRS_DEGENERATE;
-    return ctx->fail(ZKMI_ERR_VERIFICATION, "transcript: degenerate (an anchor point is infinity, or there is no tau to compare against)");
-  }
   uint32_t failed = 0;
   std::vector<PairEq> eqs;
-  if (has_tau) {
-    // the three G1 chains against [tau]G2:  e(hi, G2) e(-lo, tau_g2[1]) = 1
-    struct {
-      const G1Affine* chain;
-      uint64_t m;
-      uint32_t dom, bit;
-    } const chains[3] = {{srs->tau_g1, srs->n_tau_g1, 0, ZKMI_SRS_BAD_TAU_G1},
-                         {srs->alpha_tau_g1, srs->n_ab, 2, ZKMI_SRS_BAD_ALPHA},
-                         {srs->beta_tau_g1, srs->n_ab, 3, ZKMI_SRS_BAD_BETA}};
-    for (const auto& c : chains) {
-      uint8_t lo_w[96], hi_w[96];
-      if ((rc = weighted_sums<1>(ctx, c.chain, nullptr, c.m, seed, c.dom, true, lo_w, hi_w)) != ZKMI_OK) return rc;
-      G1Affine lo, hi;
-      if (!wire_g1(lo_w, &lo) || !wire_g1(hi_w, &hi)) return ctx->fail(ZKMI_ERR_HIP, "ceremony: the MSM returned a non-canonical point");
-      eqs.push_back({hi, g2_generator(), lo.neg(), tau2, c.bit});
-    }
-    // the G2 chain against [tau]G1:  e(tau_g1[1], lo) e(-G1, hi) = 1; its term i = 0 ties tau in G1 to tau in G2
-    uint8_t lo_w[192], hi_w[192];
-    if ((rc = weighted_sums<2>(ctx, srs->tau_g2, nullptr, srs->n_tau_g2, seed, 1, true, lo_w, hi_w)) != ZKMI_OK) return rc;
-    G2Affine lo, hi;
-    if (!wire_g2(lo_w, &lo) || !wire_g2(hi_w, &hi)) return ctx->fail(ZKMI_ERR_HIP, "ceremony: the MSM returned a non-canonical point");
-    eqs.push_back({tau1, lo, g1_generator().neg(), hi, ZKMI_SRS_BAD_TAU_G2});
+  SrsAnchors an;
+  if ((rc = srs_consistency(ctx, srs, seed, &an, &failed, &eqs)) != ZKMI_OK) return rc;
+  if (failed & ZKMI_SRS_DEGENERATE) {
+    *out_failed = failed;
+    return ctx->fail(ZKMI_ERR_VERIFICATION, "transcript: degenerate (an anchor point is infinity, or there is no tau to compare against)");
   }
-  // beta in G1 and in G2:  e(beta_tau_g1[0], G2) e(-G1, beta_g2) = 1
-  eqs.push_back({beta0, g2_generator(), g1_generator().neg(), srs->beta_g2, ZKMI_SRS_BAD_BETA_G2});
   if ((rc = pair_equations(ctx, eqs, &failed)) != ZKMI_OK) return rc;
   *out_failed = failed;
   return failed ? ctx->fail(ZKMI_ERR_VERIFICATION, "transcript: failed checks, mask " + std::to_string(failed)) : ZKMI_OK;
+}
+
+int32_t zkmi_srs_verify_contribution(zkmi_ctx* ctx, const zkmi_srs* before, const zkmi_srs* after, const uint8_t step_g2[576],
+                                     const uint8_t seed_in[32], uint32_t* out_failed) {
+  ZK_ENTER(ctx);
+  if (!before || !after || !step_g2 || !out_failed) return ZKMI_ERR_BAD_ARG;
+  *out_failed = 0;
+  int32_t rc = srs_verifiable(ctx, before);
+  if (rc == ZKMI_OK) rc = srs_verifiable(ctx, after);
+  if (rc != ZKMI_OK) return rc;
+  if (before->n_tau_g1 != after->n_tau_g1 || before->n_tau_g2 != after->n_tau_g2 || before->n_ab != after->n_ab)
+    return ctx->fail(ZKMI_ERR_BAD_ARG, "transcripts of different shape");
+  // the step elements [s]G2 | [a]G2 | [b]G2: on the curve and in the subgroup, or the pairing says nothing
+  G2Affine step[3];
+  bool step_inf = false;
+  for (int j = 0; j < 3; j++) {
+    if (!g2_from_wire(step_g2 + 192 * j, &step[j], true) || !g2_in_subgroup(step[j]))
+      return ctx->fail(ZKMI_ERR_NON_CANONICAL, "step element " + std::to_string(j) + ": not a point of the G2 subgroup");
+    step_inf = step_inf || step[j].is_inf();
+  }
+  uint8_t drawn[32];
+  const uint8_t* seed = nullptr;
+  if ((rc = draw_seed(ctx, seed_in, drawn, &seed)) != ZKMI_OK) return rc;
+  ZK_HIP(ctx, ctx->drain());
+  phases_reset();
+  uint32_t failed = 0;
+  std::vector<PairEq> eqs;
+  SrsAnchors a, b;
+  if ((rc = srs_consistency(ctx, after, seed, &a, &failed, &eqs)) != ZKMI_OK) return rc;
+  if ((rc = srs_anchors(ctx, before, &b)) != ZKMI_OK) return rc;
+  // after = before moved by the logarithms of the step elements: one equation per element, anchored on the first point of
+  // each chain that carries it.  The domain of size 1 has no tau_g1[1]: no tau step to compare.
+  const bool has_tau1 = before->n_tau_g1 > 1;
+  if (step_inf || (has_tau1 && b.tau1.is_inf()) || b.alpha0.is_inf() || b.beta0.is_inf()) {
+    failed |= ZKMI_SRS_STEP_DEGENERATE;
+  } else {
+    struct {
+      const G1Affine *now, *was;
+      const G2Affine* by;
+      uint32_t bit;
+      bool present;
+    } const steps[3] = {{&a.tau1, &b.tau1, &step[0], ZKMI_SRS_STEP_BAD_TAU, has_tau1},
+                        {&a.alpha0, &b.alpha0, &step[1], ZKMI_SRS_STEP_BAD_ALPHA, true},
+                        {&a.beta0, &b.beta0, &step[2], ZKMI_SRS_STEP_BAD_BETA, true}};
+    for (const auto& s : steps) {
+      if (!s.present) continue;
+      // e(now, G2) e(-was, step) = 1.  `was` and `step` are finite here, so e(was, step) != 1: an infinite `now` fails
+      // the equation without a Miller loop.
+      if (s.now->is_inf()) failed |= s.bit;
+      else eqs.push_back({*s.now, g2_generator(), s.was->neg(), *s.by, s.bit});
+    }
+  }
+  if ((rc = pair_equations(ctx, eqs, &failed)) != ZKMI_OK) return rc;
+  *out_failed = failed;
+  return failed ? ctx->fail(ZKMI_ERR_VERIFICATION, "transcript contribution: failed checks, mask " + std::to_string(failed)) : ZKMI_OK;
 }
 
 }  // extern "C"

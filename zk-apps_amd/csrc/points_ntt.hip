@@ -13,12 +13,18 @@
 //               reads w^-k = -w^(N/2 - k) from the same table.  Both additions are the complete one (curve.hpp
 //               XYZZ::add): P = wQ, P = -wQ and infinity all occur on legitimate inputs.
 //   k_pn_store  XYZZ -> resident affine, PN_INV_BATCH points per lane under one inversion
+//
+// A phase-1 contribution (zkmi_srs_contribute) is four calls of the per-point multiplication of points_mul.hip over the
+// transcript's arrays, under powers made on the device; no kernel of its own lives here.
 #include <string.h>
+#include <algorithm>
 #include <new>
 #include <string>
+#include <type_traits>
 #include "points_ntt.hpp"
 #include "group_dev.hpp"
 #include "points.hpp"
+#include "points_mul.hpp"
 
 namespace zkmi {
 
@@ -292,6 +298,69 @@ int32_t zkmi_srs_generate(zkmi_ctx* ctx, const uint8_t toxic[96], uint32_t log_n
   fr_words(beta, k);
   s->beta_g2 = scalar_mul(G2XYZZ::from_affine(g2), k, 8).to_affine();
   *out = s;
+  return ZKMI_OK;
+}
+
+// Where the toxic waste lives during the call, and where it ends:
+//   `sec` below     the Montgomery forms of s, a, b and the canonical words handed to the host scalar multiplications;
+//                   its destructor overwrites the whole struct on every return path
+//   pw (HBM)        the n powers c s^i of the array being multiplied, reused for the three weights 1, a, b; overwritten
+//                   with zeros (wipe_dev, then a stream wait) before the buffer is freed, on the error paths as well
+//   fr_powers_dev   the table c | s^(2^t) in pinned host memory and in HBM: wiped inside that call (points_mul.hip)
+// Not reachable from here: registers and scratch of the kernels, which the next launch overwrites.
+int32_t zkmi_srs_contribute(zkmi_ctx* ctx, zkmi_srs* srs, const uint8_t sab[96], uint8_t out_step_g2[576]) {
+  ZK_ENTER(ctx);
+  if (!srs || !sab || !out_step_g2) return ZKMI_ERR_BAD_ARG;
+  if (srs->ctx != ctx || srs->device != ctx->device) return ctx->fail(ZKMI_ERR_BAD_ARG, "transcript of another context");
+  struct Secrets {
+    Fr s, a, b;
+    uint32_t k[8];
+    ~Secrets() { wipe_host(this, sizeof(*this)); }
+  } sec;
+  if (!fr_from_wire(sab, &sec.s) || !fr_from_wire(sab + 32, &sec.a) || !fr_from_wire(sab + 64, &sec.b))
+    return ctx->fail(ZKMI_ERR_NON_CANONICAL, "contribution >= r");
+  if (sec.s.is_zero() || sec.a.is_zero() || sec.b.is_zero()) return ctx->fail(ZKMI_ERR_BAD_ARG, "contribution must be non-zero");
+  ZK_HIP(ctx, ctx->drain());  // the transcript is idle: nothing queued earlier still reads its arrays
+  points_mul_phases_reset();
+  const uint64_t n1 = srs->n_tau_g1, n2 = srs->n_tau_g2, nab = srs->n_ab;
+  const uint64_t n_pw = std::max(std::max(n1, n2), nab);
+  // fresh arrays, swapped in at the end: a failure on the way leaves the transcript as it was
+  DevBuf t1, t2, al, be, pw;
+  ZK_HIP(ctx, t1.alloc(sizeof(G1Affine) * n1));
+  ZK_HIP(ctx, t2.alloc(sizeof(G2Affine) * n2));
+  ZK_HIP(ctx, al.alloc(sizeof(G1Affine) * nab));
+  ZK_HIP(ctx, be.alloc(sizeof(G1Affine) * nab));
+  ZK_HIP(ctx, pw.alloc(32 * n_pw));
+  uint32_t* d_pw = pw.as<uint32_t>();
+  int32_t rc = fr_powers_dev(ctx, Fr::one(), sec.s, std::max(n1, n2), d_pw);
+  if (rc == ZKMI_OK) rc = points_mul_each_resident<Fq>(ctx, srs->tau_g1, d_pw, n1, t1.as<G1Affine>());
+  if (rc == ZKMI_OK) rc = points_mul_each_resident<Fq2>(ctx, srs->tau_g2, d_pw, n2, t2.as<G2Affine>());
+  if (rc == ZKMI_OK) rc = fr_powers_dev(ctx, sec.a, sec.s, nab, d_pw);
+  if (rc == ZKMI_OK) rc = points_mul_each_resident<Fq>(ctx, srs->alpha_tau_g1, d_pw, nab, al.as<G1Affine>());
+  if (rc == ZKMI_OK) rc = fr_powers_dev(ctx, sec.b, sec.s, nab, d_pw);
+  if (rc == ZKMI_OK) rc = points_mul_each_resident<Fq>(ctx, srs->beta_tau_g1, d_pw, nab, be.as<G1Affine>());
+  const hipError_t ew = wipe_dev(pw.p, 32 * n_pw, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (rc != ZKMI_OK) return rc;
+  ZK_HIP(ctx, ew);
+  ZK_HIP(ctx, es);
+  // the single elements on the host: b beta_g2 and the three step elements
+  const G2XYZZ g2 = G2XYZZ::from_affine(g2_generator());
+  const Fr* const step[3] = {&sec.s, &sec.a, &sec.b};
+  for (int j = 0; j < 3; j++) {
+    fr_words(*step[j], sec.k);
+    g2_to_wire(scalar_mul(g2, sec.k, 8).to_affine(), out_step_g2 + 192 * j);
+  }
+  srs->beta_g2 = scalar_mul(G2XYZZ::from_affine(srs->beta_g2), sec.k, 8).to_affine();  // sec.k holds b
+  auto swap_in = [](auto*& held, DevBuf& fresh) {  // the old array goes with the DevBuf
+    void* old = held;
+    held = static_cast<std::remove_reference_t<decltype(held)>>(fresh.p);
+    fresh.p = old;
+  };
+  swap_in(srs->tau_g1, t1);
+  swap_in(srs->tau_g2, t2);
+  swap_in(srs->alpha_tau_g1, al);
+  swap_in(srs->beta_tau_g1, be);
   return ZKMI_OK;
 }
 

@@ -116,6 +116,29 @@ int32_t zkmi_selftest_fp28_ops(zkmi_ctx* ctx, int32_t field, int32_t op, uint32_
  *    18 is_one              f -> one byte per tuple in out_flag: the status expression of k_final_exp    12 -> 0
  * An op out of range: ZKMI_ERR_BAD_ARG. */
 int32_t zkmi_selftest_tower_ops(zkmi_ctx* ctx, int32_t op, uint32_t n, const int32_t* in, int32_t* out, uint8_t* out_flag);
+/* One body of the device group law -- the layer between the field and the MSM -- on n tuples of RAW limb arrays, in the
+ * convention of the two calls above: a coordinate is NL int32 limbs (curve 0 BLS12-381 G1: 14; curve 2 BN254 G1: 10) or, for
+ * curve 1 (BLS12-381 G2), the two elements c0 then c1; a point is its coordinates X Y ZZ ZZZ, an affine point x y; nothing is
+ * converted, the caller chooses the representation x + k p of every coordinate.  ctx != NULL: on the device, in 64-lane blocks,
+ * tail lanes shadowing the last tuple and writing nothing; ctx == NULL: the same body in a host loop.  Every op writes the
+ * four coordinates of one point per tuple to out.  tests/group28.py holds the big-integer model.  n <= 65536.
+ *   op   body                                             in -> out                          out_flag (one byte per tuple)
+ *    0 1 madd_generic, negmask 0 / ~0  (msm_impl.hpp)     acc (X Y ZZ ZZZ), p (x y) -> acc    the returned bool
+ *    2 3 madd_affine_pair, negmask 0 / ~0                 acc (x y), p (x y) -> acc           the returned bool
+ *                                                         (ZZ = ZZZ = 0 where it returned false: the body never reads them)
+ *    4   add_generic                                      a, o -> a                           the returned bool
+ *    5   XYZZ::add  6 XYZZ::madd  7 XYZZ::dbl_inplace  (curve.hpp)   a, o / a, p / a -> a     -
+ *    8 9 XYZZQ::add, DPP form / ds_bpermute form  (quad.hpp)         a, o -> a                -
+ *   10   chain of K = 16 table entries (x y each) and K sign words behind them (non-zero: the entry is subtracted): the first
+ *        entry with its sign applied as accum_first applies it, madd_affine_pair of the second, madd_generic of the others
+ *        until one returns false -> acc as it stands (ZZ = ZZZ = 0 if the pair step returned false); out_flag: the index
+ *        1 .. 15 of the entry that returned false, 0xFF if none
+ *   Ops 0 - 4 and 10 run in the lane layout of the accumulation kernels: OneLane for curves 0 and 2, LanePair over Fq2P for
+ *   curve 1; ops 5 - 7 one lane per point; ops 8 and 9 a quad per point (curve 1: an octet).
+ *   Host path: ops 0 - 7 and 10 for curves 0 and 2; ops 4 - 7 for curve 1 (over Fq2_28; the Fq2P forms are DPP code).
+ * An op the curve or the path does not have: ZKMI_ERR_BAD_ARG. */
+int32_t zkmi_selftest_group_ops(zkmi_ctx* ctx, int32_t curve, int32_t op, uint32_t n, const int32_t* in, int32_t* out,
+                                uint8_t* out_flag);
 /* The same tower templates over an INTERVAL type, on the host: every Fq2 value is a closed interval in units of p, sums
  * propagate it, a product records its operands and returns the (-1/2, 3/2) a Montgomery product promises, shrink records its
  * input and returns (-2, 2).  Runs the Miller loop from the kernels' entry conditions, e12_mul of two shrunk values, e12_conj

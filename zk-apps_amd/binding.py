@@ -192,6 +192,8 @@ class Zkmi:
                 if mine != theirs:
                     self._tlib = None
                     raise ZkmiError(-1, f"libzkmi.so and libzkmi_exp.so disagree on struct layouts: {mine} vs {theirs}; rebuild both")
+            self._tlib.zkmi_selftest_group_ops.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p]
         return self._tlib
 
     @staticmethod

@@ -23,8 +23,10 @@
 //     1260 p^2; two lazy sums of 16 p values reach 1024 p^2).  The pairing
 //     tower (tower_dev.hpp) works to that condition with operands up to
 //     22.5 p and sums up to 202.5 p^2.
-//   * is_zero() is exact for |v| <= 4p, which covers products, Fq2 products and
-//     canonical inputs — the only places it is called (see curve.hpp).
+//   * is_zero() is exact for |v| <= 4p, which covers what it is called on: products
+//     and Fq2 products (the squares P^2, R^2 of the group law), canonical inputs, and
+//     the STORED coordinates the infinity tests read -- ZZ of a point in (-p/2, 3p/2),
+//     x and +-y of a table entry in (-3p/2, 3p/2) (curve.hpp).
 //   * to_canonical() returns the unique representative in [0, p).
 #pragma once
 #include "field.hpp"
@@ -480,6 +482,7 @@ ZK_HD Fp28<P> f_signed_sub_lazy(const Fp28<P>& a, uint32_t m, const Fp28<P>& b) 
   for (int i = 0; i < P::NL; i++) r.l[i] = (int32_t)(((uint32_t)a.l[i] ^ m) - m) - b.l[i];
   return r;
 }
+// rr - ppp - 2 q of three products, carried: (-5p, 3p), the class of a stored X
 template <class P>
 ZK_HD Fp28<P> f_x3(const Fp28<P>& rr, const Fp28<P>& ppp, const Fp28<P>& q) {
   Fp28<P> r;
@@ -491,7 +494,9 @@ ZK_HD Fp28<P> f_x3(const Fp28<P>& rr, const Fp28<P>& ppp, const Fp28<P>& q) {
 // a b - c d under one reduction (a, b may be lazy differences; c, d normalised).  Range: with every operand at the
 // |v| < 16 p bound the column sum reaches (32 p)^2 + (16 p)^2 = 1280 p^2, i.e. 0.508 p after the division by R in Fq28,
 // so the result lies in (-p, 2p) -- not in the (-p/2, 3p/2) of a single product; still normalised and within is_zero()'s
-// range.  (The Fq2 form below sums four products of normalised operands: 1024 p^2, inside (-p/2, 3p/2).)
+// range.  (The Fq2 form below sums four products of normalised operands: 1024 p^2, inside (-p/2, 3p/2).)  In the group law
+// the operands are nowhere near that bound: with every coordinate at the end of its class the column sum
+// of Y3 = R (Q - X3) - Y PPP stays below 36 p^2 (G2: 60 p^2) and Y3 inside (-p/2, 3p/2); the class stated for it is (-p, 2p).
 template <class P>
 ZK_HD Fp28<P> f_mul_sub_mul(const Fp28<P>& a, const Fp28<P>& b, const Fp28<P>& c, const Fp28<P>& d) {
   constexpr int NL = P::NL;

@@ -111,7 +111,7 @@ __device__ __forceinline__ void st_comp(Fq28* p, const Fq28& v) {
 // the caller hands the bucket to k_accum_redo.  No state besides acc: the loop around it has one path.
 // negmask = 0xffffffff adds -p instead of p (the sign of the digit): folded into the lazy difference R = +-(y zzz) - Y
 template <class F>
-__device__ __forceinline__ bool madd_generic(XYZZ<F>& acc, const Affine<F>& p, uint32_t negmask = 0) {
+__host__ __device__ __forceinline__ bool madd_generic(XYZZ<F>& acc, const Affine<F>& p, uint32_t negmask = 0) {
   F pp_ = f_sub_lazy(p.x * acc.zz, acc.x);
   F r = f_signed_sub_lazy(p.y * acc.zzz, negmask, acc.y);
   F pp = pp_.sqr();
@@ -129,7 +129,7 @@ __device__ __forceinline__ bool madd_generic(XYZZ<F>& acc, const Affine<F>& p, u
 // mmadd-2008-s, 4M + 2S.  madd_generic would multiply p.x, p.y, pp and ppp by one here: four products of the ten, once per
 // bucket.  Same contract (false: p = +-acc, nothing written) and the same lazy differences; sets all four coordinates.
 template <class F>
-__device__ __forceinline__ bool madd_affine_pair(XYZZ<F>& acc, const Affine<F>& p, uint32_t negmask = 0) {
+__host__ __device__ __forceinline__ bool madd_affine_pair(XYZZ<F>& acc, const Affine<F>& p, uint32_t negmask = 0) {
   F pp_ = f_sub_lazy(p.x, acc.x);
   F r = f_signed_sub_lazy(p.y, negmask, acc.y);
   F pp = pp_.sqr();
@@ -524,7 +524,7 @@ k_accum_g1_nc(const AccumArgs<F, MULTI> args, uint32_t total_buckets) {
 }
 // acc += o for acc, o != O; false when the sum needs the complete group law (o = +-acc): same contract as madd_generic
 template <class F>
-__device__ __forceinline__ bool add_generic(XYZZ<F>& a, const XYZZ<F>& o) {
+__host__ __device__ __forceinline__ bool add_generic(XYZZ<F>& a, const XYZZ<F>& o) {
   F u1 = a.x * o.zz;
   F u2 = o.x * a.zz;
   F s1 = a.y * o.zzz;

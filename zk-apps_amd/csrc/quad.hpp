@@ -22,8 +22,11 @@
 // count: they are placed beside them.  All branches are quad-uniform (flags are broadcast inside the quad before they are
 // tested), which is what DPP needs: a disabled source lane would read as zero.
 //
-// Value ranges (field28.hpp): products leave (-p/2, 3p/2); the lazy differences d, Q - X3 have limbs below 2^29 and only
-// feed products; X3 and Y3 are carried differences of at most four products (|v| < 6p < 16p).
+// Value ranges (field28.hpp; DESIGN.md 5.1.1 derives the classes, tests/group28.py holds every op to them): products leave
+// (-p/2, 3p/2); the lazy differences d, Q - X3 have limbs below 2^29 and only feed products; X3 = RR - PPP - 2 Q is a carried
+// sum in (-5p, 3p) (the doubling's M^2 - 2 S: (-7p/2, 5p/2)) and Y3 a carried difference of two products in (-2p, 2p) -- the
+// classes every consumer of a stored point accepts.  is_inf() runs is_zero() in every lane, also on an X beyond its 4 p
+// range: only lane 2's answer (ZZ, a product) is read.
 #pragma once
 #include "curve.hpp"
 #include "field28.hpp"

@@ -198,6 +198,39 @@ int32_t zkmi_selftest_msm_g1_sum2_dev(zkmi_ctx* ctx, const void* d_scalars_a, co
  * n_out != 37: ZKMI_ERR_BAD_ARG. */
 int32_t zkmi_selftest_msm_run_schedule(uint64_t n, int32_t shared, uint64_t plan_n, int32_t engine, int32_t host_spin, int32_t nm,
                                        int32_t flags, int32_t* out, uint32_t n_out);
+/* The digit sort every MSM starts with (csrc/msm_sort.hip), read out: tests/sort_model.py is the numpy model of its contract.
+ * sort_shape: the constants its kernel chains switch on, for tests that place their cases around them.  out[13], in this order:
+ *   FINE_LOG, FINE_STAGE, FINE_ROUND, FSORT_RPT, BIG_THR, BIG_MAX, BIG_NCH, SPLIT_B, PART_MAX, FPART_BLOCKS, MSM_HEAVY,
+ *   MSM_HEAVY_CAP, the scalars per batch of the staged write passes.  n_out != 13: ZKMI_ERR_BAD_ARG.
+ * sort_dev: one run of the context's own sort (ctx->sort) over n canonical 32-byte scalars in HBM (they are not checked: the
+ * MSM entry points that take device scalars do not check them either), reserved as the product entry point of that mode
+ * reserves it; waits for the stream and copies the result out.
+ *   mode 0  run(): the windowed plan of n terms; plan_n != 0: n terms under the window width of the plan of plan_n terms,
+ *           buffers reserved for plan_n, as zkmi_msm_g1_windows_dev sorts a slice (plan_n < n counts as n)
+ *   mode 1  run_shared(): the shared-bucket plan of prepared bases
+ *   mode 2  run_shared_batch(): `batch` vectors of n scalars one behind another (vector v at d_scalars + 32 n v bytes)
+ *   plan_n with a mode other than 0, batch != 0 with a mode other than 2, batch x partitions per vector > 64, n = 0 or
+ *   above the MSM's limit: ZKMI_ERR_BAD_ARG.
+ * out_info[16] (n_info != 16: ZKMI_ERR_BAD_ARG), the plan and what ran:
+ *   [0] c  [1] nwin  [2] nb  [3] ndigits  [4] shared  [5] vec_parts  [6] heavy_thr  [7] heavy_shift  [8] top_spread_log
+ *   [9] buckets in all (nwin x nb)
+ *   [10] words of sorted[] in use: nwin x n for the plain windowed chain (window w owns [w n, (w + 1) n)), the number of
+ *        records for every other chain (sorted[] is packed)
+ *   [11] heavy[0], the number of heavy buckets
+ *   [12] log2 of the buckets per fine partition (paths 2 and 5, else 0)
+ *   [13] oversized fine partitions listed for the k_big_* kernels (path 2, else 0), [14] fine partitions above BIG_THR records
+ *        in all: those beyond the list stay with the round form of k_fpart_sort
+ *   [15] the kernel chain that ran (csrc/msm.hpp MsmSortPath): 1 plain windowed, 2 two-level / big windowed in its fine form,
+ *        3 big windowed in its record form, 4 shared with one partition, 5 shared fine-partition form, 6 shared record form,
+ *        7 shared batch
+ * out_count, out_begin, out_perm: [9] words each; out_heavy: 1 + [9] words of which 1 + [11] are written (heavy[0], then the
+ * ids); out_sorted: [10] words.  Any of them may be NULL (call once for out_info, then with room); cap_buckets below [9] or
+ * cap_sorted below [10] with the array given: ZKMI_ERR_BAD_ARG (out_info is written first). */
+int32_t zkmi_selftest_msm_sort_shape(uint32_t* out, uint32_t n_out);
+int32_t zkmi_selftest_msm_sort_dev(zkmi_ctx* ctx, int32_t mode, const void* d_scalars, uint64_t n, uint64_t plan_n,
+                                   uint32_t batch, uint32_t* out_info, uint32_t n_info,
+                                   uint32_t* out_count, uint32_t* out_begin, uint32_t* out_perm, uint32_t* out_heavy,
+                                   uint64_t cap_buckets, uint32_t* out_sorted, uint64_t cap_sorted);
 /* The column sums of zkmi_groth16_setup_from_srs without a device: csrc/colsum_plan.hpp, csrc/setup_srs.hip.
  * which numbers the query as zkmi_pk_export_query does: 0 a, 1 b_g1, 2 b_g2, 4 l (all n_vars slots; the first n_pub of l
  * are gamma_abc_g1).

@@ -590,6 +590,17 @@ class Zkmi:
         self._chk(self.tlib.zkmi_selftest_points_mul_shape(C.byref(chunk), C.byref(window)))
         return int(chunk.value), int(window.value)
 
+    MSM_SORT_SHAPE = ("FINE_LOG", "FINE_STAGE", "FINE_ROUND", "FSORT_RPT", "BIG_THR", "BIG_MAX", "BIG_NCH", "SPLIT_B", "PART_MAX",
+                      "FPART_BLOCKS", "MSM_HEAVY", "MSM_HEAVY_CAP", "WRITE_BATCH")
+    MSM_SORT_INFO = ("c", "nwin", "nb", "ndigits", "shared", "vec_parts", "heavy_thr", "heavy_shift", "top_spread_log", "buckets",
+                     "words", "n_heavy", "fine_log", "big_listed", "big_total", "path")
+
+    def selftest_msm_sort_shape(self):
+        """Testing library: the constants the digit sort's kernel chains switch on (csrc/msm_sort.hip), as a dict."""
+        out = (C.c_uint32 * len(self.MSM_SORT_SHAPE))()
+        self._chk(self.tlib.zkmi_selftest_msm_sort_shape(out, C.c_uint32(len(self.MSM_SORT_SHAPE))))
+        return dict(zip(self.MSM_SORT_SHAPE, (int(v) for v in out)))
+
     def points_mul_kernel(self, which):
         """Testing library: the multiplication kernel ITS calls launch from now on: 0 windowed, 1 plain, -1 as the environment said."""
         self._chk(self.tlib.zkmi_points_mul_kernel(C.c_int32(which)))
@@ -1022,6 +1033,27 @@ class Context:
         out = (C.c_uint8 * 96)()
         self._chk(self.z.tlib.zkmi_selftest_msm_g1_sum2_dev(self.h, C.c_void_p(dptr_a), C.c_void_p(dptr_b), C.c_uint64(n), bases.h, out))
         return bytes(out)
+
+    def selftest_msm_sort_dev(self, dptr, n, mode=0, plan_n=0, batch=0, arrays=True):
+        """Testing library: one run of this context's digit sort over n canonical scalars in HBM, read out (mode 0 windowed --
+        plan_n: under the window width of that many terms --, 1 shared, 2 shared batch of `batch` vectors).  Returns
+        (info dict, count, begin, perm, heavy, sorted) as ctypes uint32 arrays (numpy reads them with np.frombuffer); heavy is
+        [n_heavy, ids ...].  arrays=False: the info dict alone.  An error code raises ZkmiError."""
+        fn = self.z.tlib.zkmi_selftest_msm_sort_dev
+        keys = self.z.MSM_SORT_INFO
+        info = (C.c_uint32 * len(keys))()
+        head = (self.h, C.c_int32(mode), C.c_void_p(dptr), C.c_uint64(n), C.c_uint64(plan_n), C.c_uint32(batch), info, C.c_uint32(len(keys)))
+        self._chk(fn(*head, None, None, None, None, C.c_uint64(0), None, C.c_uint64(0)))
+        d = dict(zip(keys, (int(v) for v in info)))
+        if not arrays:
+            return d
+        nb, nw = d["buckets"], d["words"]
+        count, begin, perm = (C.c_uint32 * nb)(), (C.c_uint32 * nb)(), (C.c_uint32 * nb)()
+        heavy, srt = (C.c_uint32 * (nb + 1))(), (C.c_uint32 * max(1, nw))()
+        self._chk(fn(*head, count, begin, perm, heavy, C.c_uint64(nb), srt, C.c_uint64(nw)))
+        # (the sort ran twice: the order inside a bucket aside, the same result)
+        assert dict(zip(keys, (int(v) for v in info))) == d, (d, list(info))
+        return d, count, begin, perm, heavy, srt
 
     def msm_g1_window_range_dev(self, dptr, n, bases, plan_n, w_first, w_count):
         """(w_count x 96 B window sums over ALL n points, total windows of the plan, window bits): a rank of a WINDOW split"""

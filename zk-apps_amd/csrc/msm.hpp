@@ -85,6 +85,18 @@ MsmPlan msm_make_plan_c(uint64_t n, int c);
 MsmPlan msm_make_plan_shared(uint64_t n);
 MsmPlan msm_make_plan_shared_batch(uint64_t n, uint32_t batch);  // the plan MsmSort::run_shared_batch(n, .., batch) will use
 
+// the kernel chains of the digit sort (msm_sort.hip), as MsmSort::last_path names them
+enum MsmSortPath {
+  MSM_SORT_NONE = 0,
+  MSM_SORT_WINDOWED = 1,     // run(): LDS-histogram tiles per (chunk, window), sorted[] in regions w * n
+  MSM_SORT_BIG_FINE = 2,     // run_windowed_big(): two-level record sort into fine partitions (big plans, 16-bit windows from 2^21 terms)
+  MSM_SORT_BIG_RECORDS = 3,  // run_windowed_big(): records per 2^15-bucket group, then LDS-histogram tiles
+  MSM_SORT_SHARED_ONE = 4,   // run_shared(): one partition, tiles scan the scalars
+  MSM_SORT_SHARED_FINE = 5,  // run_shared(): records per fine partition, one workgroup each (k_fpart_sort)
+  MSM_SORT_SHARED_RECORDS = 6,  // run_shared(): records per partition, then LDS-histogram tiles
+  MSM_SORT_SHARED_BATCH = 7  // run_shared_batch()
+};
+
 // Bucket scatter: signed-digit decomposition + counting sort of point indices
 // by (window, bucket).  Shared by every MSM over the same scalar vector.
 struct MsmSort {
@@ -109,6 +121,9 @@ struct MsmSort {
   // run_windowed_big: log2 of the buckets per LDS-histogram tile -- 15 (128 KB of counters: a CU to itself) or 14 (64 KB: fits
   // beside an occupancy-capped accumulation, MSM_RUN_TWO_WAVES); 14 only for window ranges WITHOUT the plan's top window
   int big_nb_log = 15;
+  // which kernel chain the last run*() queued: an MsmSortPath, for run_windowed_big's fine form with the log2 of the buckets per
+  // fine partition in bits 8.. (written by run*(), read by the testing library's zkmi_selftest_msm_sort_dev only)
+  int last_path = 0;
   // events of kernels on OTHER streams that still read count/begin/heavy/sorted (the heavy-bucket
   // kernels of MsmEngine::run_device): the next sort waits for them before it overwrites the buffers
   mutable std::vector<hipEvent_t> readers;

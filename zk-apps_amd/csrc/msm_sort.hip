@@ -1497,6 +1497,7 @@ hipError_t MsmSort::run(const uint32_t* d_scalars, uint64_t n, hipStream_t st, P
       }
     }
   }
+  last_path = MSM_SORT_WINDOWED;
   if (prof) prof->begin(PH_MSM_SORT, st);
   const size_t lds = sizeof(uint32_t) * nb;
   const dim3 grid(nch, nwin);
@@ -1565,6 +1566,7 @@ hipError_t MsmSort::run_windowed_big(const uint32_t* d_scalars, uint64_t n, hipS
   const uint32_t NPF = tot_b >> fine_log;
   if (nb_log == 15 && NPF <= FINE_BIG_PARTS && rec_aux != nullptr && big_ws != nullptr && ZK_TUNE("ZKMI_BIG_SORT", 1) != 0) {
     const int fan_log = nb_log - fine_log;
+    last_path = MSM_SORT_BIG_FINE | (fine_log << 8);
     hipError_t e = hipMemsetAsync(fpart + NPF, 0, sizeof(uint32_t) * NPF, st);
     if (e != hipSuccess) return e;
     // (bucket ids travel as 16-bit words through the three levels; rec_aux / rec_bkt are sized for 32-bit ones)
@@ -1600,6 +1602,7 @@ hipError_t MsmSort::run_windowed_big(const uint32_t* d_scalars, uint64_t n, hipS
     return hipGetLastError();
   }
   if ((uint64_t)tot_b * nch > cap_hist) return hipErrorInvalidValue;
+  last_path = MSM_SORT_BIG_RECORDS;
   hipLaunchKernelGGL((k_part_pass<false, true>), dim3(nblk), dim3(nb_log == 14 ? 512 : 1024), 0, st, d_scalars, (uint32_t)n, plan.c, (int)nwin, nb, nb_log, P,
                      chunk, rc, blkcnt, rec_entry, rec_bkt, plan.win_first, w_top_pos);
   hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(PART_MAX), 0, st, blkcnt, nblk, P, part_total);
@@ -1661,6 +1664,7 @@ hipError_t MsmSort::run_shared(const uint32_t* d_scalars, uint64_t n, hipStream_
   const bool fine_fits = NP <= FINE_MAX_PARTS && (uint64_t)plan.ndigits * n / (NP ? NP : 1) <= 2 * FINE_ROUND &&
                          plan.ndigits <= (int)FPASS_MAXD;
   if (records && fine_mode != 0 && (fine_mode == 2 ? NP <= FINE_MAX_PARTS : fine_fits) && fpart != nullptr) {
+    last_path = MSM_SORT_SHARED_FINE;
     uint32_t nblk = (uint32_t)((n + 4095) / 4096);
     if (nblk > FPART_BLOCKS) nblk = FPART_BLOCKS;
     const uint32_t chunk_a = (uint32_t)((n + nblk - 1) / nblk);
@@ -1703,6 +1707,7 @@ hipError_t MsmSort::run_shared(const uint32_t* d_scalars, uint64_t n, hipStream_
     if (prof) prof->end(PH_MSM_SORT, st);
     return hipGetLastError();
   }
+  last_path = records ? MSM_SORT_SHARED_RECORDS : MSM_SORT_SHARED_ONE;
   uint32_t nblk_a = 0, chunk_a = 0;
   if (records) {
     nblk_a = (uint32_t)((n + 4095) / 4096);
@@ -1784,6 +1789,7 @@ hipError_t MsmSort::run_shared_batch(const uint32_t* d_scalars, uint64_t n, uint
             (unsigned long long)n, batch, nb, nch, chunk, plan.c, plan.ndigits);
   };
   chk("entry");
+  last_path = MSM_SORT_SHARED_BATCH;
   if (prof) prof->begin(PH_MSM_SORT, st);
   const size_t lds = sizeof(uint32_t) * nb;
   const dim3 grid(nch, P);
@@ -1863,3 +1869,76 @@ void PhaseTimer::reset() {
 }
 
 }  // namespace zkmi
+
+// One run of the context's own sort, read out (include/zkmi_testing.h; tests/sort_model.py holds the model of its contract).
+#ifdef ZKMI_TESTING  // test scaffolding: libzkmi_exp.so only (include/zkmi_testing.h)
+#include "ctx.hpp"
+extern "C" int32_t zkmi_selftest_msm_sort_shape(uint32_t* out, uint32_t n_out) {
+  using namespace zkmi;
+  // (the staged write passes -- k_fpart_write_staged, k_part_write_staged -- rank one scalar per thread of a 1024-thread block)
+  const uint32_t v[] = {(uint32_t)FINE_LOG, FINE_STAGE, FINE_ROUND, FSORT_RPT, BIG_THR, BIG_MAX, BIG_NCH, SPLIT_B,
+                        PART_MAX, FPART_BLOCKS, MSM_HEAVY, MSM_HEAVY_CAP, 1024u};
+  if (!out || n_out != sizeof(v) / sizeof(v[0])) return ZKMI_ERR_BAD_ARG;
+  for (uint32_t i = 0; i < n_out; i++) out[i] = v[i];
+  return ZKMI_OK;
+}
+extern "C" int32_t zkmi_selftest_msm_sort_dev(zkmi_ctx* ctx, int32_t mode, const void* d_scalars, uint64_t n, uint64_t plan_n,
+                                              uint32_t batch, uint32_t* out_info, uint32_t n_info, uint32_t* out_count,
+                                              uint32_t* out_begin, uint32_t* out_perm, uint32_t* out_heavy, uint64_t cap_buckets,
+                                              uint32_t* out_sorted, uint64_t cap_sorted) {
+  using namespace zkmi;
+  ZK_ENTER(ctx);
+  if (!d_scalars || !out_info || n_info != 16 || n == 0 || n > MSM_MAX_TERMS || plan_n > MSM_MAX_TERMS || mode < 0 || mode > 2 ||
+      (plan_n && mode != 0) || (mode == 2) != (batch != 0))
+    return ZKMI_ERR_BAD_ARG;
+  if (mode == 2 && (uint64_t)batch * msm_make_plan_shared(n).nwin > 64) return ZKMI_ERR_BAD_ARG;
+  MsmSort& s = ctx->sort;
+  const uint32_t* sc = static_cast<const uint32_t*>(d_scalars);
+  s.last_path = MSM_SORT_NONE;
+  if (mode == 0) {
+    if (plan_n && plan_n < n) plan_n = n;
+    ZK_HIP(ctx, s.reserve(plan_n ? plan_n : n));
+    if (plan_n) s.plan_override = msm_make_plan(plan_n).c;
+    const hipError_t e = s.run(sc, n, ctx->stream, ctx->timer());
+    s.plan_override = 0;
+    if (e != hipSuccess) return ctx->hip_fail(e, "sort");
+  } else if (mode == 1) {
+    ZK_HIP(ctx, s.reserve(n, true));
+    ZK_HIP(ctx, s.run_shared(sc, n, ctx->stream, ctx->timer()));
+  } else {
+    ZK_HIP(ctx, s.reserve(n, true));
+    ZK_HIP(ctx, s.reserve_batch(n, batch));
+    ZK_HIP(ctx, s.run_shared_batch(sc, n, 8ull * n, batch, ctx->stream, ctx->timer()));
+  }
+  ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const MsmPlan& pl = s.plan;
+  const int path = s.last_path & 0xff;
+  const uint64_t tot_b = (uint64_t)pl.nwin * pl.nb;
+  uint64_t words = (uint64_t)pl.nwin * n;
+  if (path != MSM_SORT_WINDOWED) {
+    // packed chains: the records per partition / group the sort itself left in part_total (the fine-partition form: all in [0])
+    const uint32_t P = plan_is_big(pl) ? (uint32_t)pl.nwin * big_parts_per_window(pl) : (uint32_t)pl.nwin;
+    if (P > PART_MAX) return ctx->fail(ZKMI_ERR_BAD_ARG, "sort read-out: more groups than part_total holds");
+    uint32_t pt[PART_MAX];
+    ZK_HIP(ctx, hipMemcpy(pt, s.part_total, sizeof(uint32_t) * P, hipMemcpyDeviceToHost));
+    words = 0;
+    for (uint32_t q = 0; q < P; q++) words += pt[q];
+  }
+  uint32_t n_heavy = 0, n_big = 0;
+  ZK_HIP(ctx, hipMemcpy(&n_heavy, s.heavy, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (path == MSM_SORT_BIG_FINE) ZK_HIP(ctx, hipMemcpy(&n_big, s.big_ws, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  const uint32_t info[16] = {(uint32_t)pl.c, (uint32_t)pl.nwin, pl.nb, (uint32_t)pl.ndigits, pl.shared ? 1u : 0u, (uint32_t)pl.vec_parts,
+                             pl.heavy_thr, (uint32_t)pl.heavy_shift, (uint32_t)pl.top_spread_log, (uint32_t)tot_b, (uint32_t)words, n_heavy,
+                             path == MSM_SORT_BIG_FINE ? (uint32_t)(s.last_path >> 8) : path == MSM_SORT_SHARED_FINE ? (uint32_t)FINE_LOG : 0u,
+                             n_big < BIG_MAX ? n_big : BIG_MAX, n_big, (uint32_t)path};
+  for (int i = 0; i < 16; i++) out_info[i] = info[i];
+  if (tot_b > s.cap_buckets || words > s.cap_entries || n_heavy > tot_b) return ctx->fail(ZKMI_ERR_BAD_ARG, "sort read-out: counts beyond the buffers");
+  if (((out_count || out_begin || out_perm || out_heavy) && cap_buckets < tot_b) || (out_sorted && cap_sorted < words)) return ZKMI_ERR_BAD_ARG;
+  if (out_count) ZK_HIP(ctx, hipMemcpy(out_count, s.count, sizeof(uint32_t) * tot_b, hipMemcpyDeviceToHost));
+  if (out_begin) ZK_HIP(ctx, hipMemcpy(out_begin, s.begin, sizeof(uint32_t) * tot_b, hipMemcpyDeviceToHost));
+  if (out_perm) ZK_HIP(ctx, hipMemcpy(out_perm, s.perm, sizeof(uint32_t) * tot_b, hipMemcpyDeviceToHost));
+  if (out_heavy) ZK_HIP(ctx, hipMemcpy(out_heavy, s.heavy, sizeof(uint32_t) * (1 + (uint64_t)n_heavy), hipMemcpyDeviceToHost));
+  if (out_sorted && words) ZK_HIP(ctx, hipMemcpy(out_sorted, s.sorted, sizeof(uint32_t) * words, hipMemcpyDeviceToHost));
+  return ZKMI_OK;
+}
+#endif  // ZKMI_TESTING

@@ -743,15 +743,7 @@ def test_update_note_relation_hashes_match_oracle(zk):
         r1.free()
 
 
-def _oracle_r1cs(r1):
-    from oracle import groth16 as g16
-
-    rows = []
-    for m in range(3):
-        rp, cl, vl = r1.export(m)
-        vals = [int.from_bytes(vl[32 * k : 32 * k + 32], "little") for k in range(len(cl))]
-        rows.append([[(cl[k], vals[k]) for k in range(rp[i], rp[i + 1])] for i in range(r1.n_constraints)])
-    return g16.R1CS(r1.n_vars, r1.n_pub, *rows)
+from note_update_cases import oracle_r1cs as _oracle_r1cs  # noqa: E402  (shared with test_cpu_note_update_edges.py)
 
 
 def test_update_note_relation_tree_height_is_a_runtime_field(zk, pkg):

@@ -349,7 +349,6 @@ int32_t synthesize(uint32_t log_n, int32_t op_kind, const zkmi_note_update& in, 
     else new_bal[hit] = op_kind == ZKMI_OP_DEPOSIT ? acc[2 * hit + 1].v + amount.v : acc[2 * hit + 1].v - amount.v;
     if (acc[0].v == acc[2].v) status = ZKMI_ERR_ACCOUNT_UPDATE;  // slots must hold distinct tokens
   }
-  if (!(priv_user.v == user.v) && status == ZKMI_OK) status = ZKMI_ERR_OPERATION_COMBINE;
 
   // ---- update_note_circuit ----
   // patch the derived note fields before they are hashed: the circuit recomputes them
@@ -401,7 +400,9 @@ int32_t synthesize(uint32_t log_n, int32_t op_kind, const zkmi_note_update& in, 
   LC nb1 = op_kind == ZKMI_OP_DEPOSIT ? Builder::add(acc[3], d1) : Builder::sub(acc[3], d1);
   // checked_add / checked_sub on u128 (account.rs:46-49, 66-69)
   const bool fit0 = b.range(nb0, BALANCE_BITS), fit1 = b.range(nb1, BALANCE_BITS);
-  if (!(fit0 && fit1) && status == ZKMI_OK) status = ZKMI_ERR_ACCOUNT_UPDATE;
+  if (!(fit0 && fit1)) status = ZKMI_ERR_ACCOUNT_UPDATE;
+  // Operation::combine last: every failure of Account::update (no slot, equal tokens, a balance out of range) comes first
+  if (!(priv_user.v == user.v) && status == ZKMI_OK) status = ZKMI_ERR_OPERATION_COMBINE;
   b.enforce_equal(b.hash({acc[0], nb0, acc[2], nb1}), new_acc_hash);
 
   // ---- padding chain up to constraints + publics = N, variables = N ----

@@ -165,7 +165,6 @@ ZK_HD int32_t rv_update_note(const zkmi_note_update& in, int32_t op_kind, int RV
   else if (hit1) nb1 = op_kind == ZKMI_OP_DEPOSIT ? acc[3] + amount : acc[3] - amount;
   else status = ZKMI_ERR_ACCOUNT_UPDATE;
   if (rv_is_zero(acc[0] - acc[2])) status = ZKMI_ERR_ACCOUNT_UPDATE;
-  if (!rv_is_zero(priv_user - user) && status == ZKMI_OK) status = ZKMI_ERR_OPERATION_COMBINE;
 
   // the two account hashes are loaded witnesses of the notes: compute them first, without emission
   NullSink quiet;
@@ -232,7 +231,9 @@ ZK_HD int32_t rv_update_note(const zkmi_note_update& in, int32_t op_kind, int RV
   const Fr28 c0 = op_kind == ZKMI_OP_DEPOSIT ? acc[1] + d0 : acc[1] - d0;
   const Fr28 c1 = op_kind == ZKMI_OP_DEPOSIT ? acc[3] + d1 : acc[3] - d1;
   const bool fit0 = rv_range(c0, out), fit1 = rv_range(c1, out);
-  if (!(fit0 && fit1) && status == ZKMI_OK) status = ZKMI_ERR_ACCOUNT_UPDATE;
+  if (!(fit0 && fit1)) status = ZKMI_ERR_ACCOUNT_UPDATE;
+  // Operation::combine last, as in relation.hip's synthesize: every failure of Account::update comes first
+  if (!rv_is_zero(priv_user - user) && status == ZKMI_OK) status = ZKMI_ERR_OPERATION_COMBINE;
   const Fr28 cv[4] = {acc[0], c0, acc[2], c1};
   rv_hash(cv, 4, c, out);
 

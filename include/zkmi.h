@@ -357,6 +357,46 @@ int32_t zkmi_poseidon_merkle_paths_dev(zkmi_ctx* ctx, const void* d_nodes, uint3
 int32_t zkmi_poseidon_merkle_roots_dev(zkmi_ctx* ctx, int32_t field, const void* d_leaves, const void* d_shape,
                                        const void* d_paths, uint32_t depth, uint64_t n, void* d_roots);
 
+/* ---- the resident Poseidon note tree: batched appends, roots and paths in HBM ---- *
+ * The relation's tree of merkle_proof.rs:38-61 (NOT the contract's SHA-256 tree above), append-only, at any height the
+ * relation admits.  One rule: a tree of height h holding n leaves is the dense tree of
+ * zkmi_poseidon_merkle_tree_dev(field, log_leaves = h) over those n leaves followed by 2^h - n zero leaves, byte for
+ * byte: the root, every stored node, every path sibling.  The padding is never materialised: with Z_0 = 0 and
+ * Z_{l+1} = hash_fix_len_array([Z_l, Z_l]), level l stores its filled prefix of ceil(n / 2^l) nodes, and a child or
+ * sibling behind it is Z_l; the root of the empty tree is Z_h.  Shape bytes are those of
+ * zkmi_poseidon_merkle_paths_dev (0: the sibling is the left input).
+ * An append of m leaves hashes sum_l ((n+m-1 >> l) - (n >> l) + 1) nodes, not 2^h.
+ * create allocates every level once (sum_l ceil(capacity / 2^l) nodes plus the Z table; nothing is reallocated later);
+ * a failed allocation is ZKMI_ERR_HIP with *out NULL.  field: ZKMI_FIELD_*; height 1..ZKMI_MAX_TREE_HEIGHT; capacity
+ * 1..2^height leaves.
+ * ZKMI_ERR_BAD_ARG, with nothing changed: a NULL argument (the optional ones excepted), m = 0, a bad field, height or
+ * capacity, n + m > capacity, a leaf_idx[i] >= n, a tree of another context or device, a device pointer of leaves,
+ * roots or paths that is not 16-byte aligned.
+ * ZKMI_ERR_NON_CANONICAL: a leaf >= the field's modulus.  The host entry checks on the host; _dev checks on the device
+ * before any node is written (one flag, read back).
+ * A refused append changes nothing: shape, root and every path are what they were, and the leaf count advances only
+ * after the call has waited for its launches.  Every call waits for its result; one context means one thread. */
+typedef struct zkmi_note_tree zkmi_note_tree;
+int32_t zkmi_note_tree_create(zkmi_ctx* ctx, int32_t field, uint32_t height, uint64_t capacity, zkmi_note_tree** out);
+int32_t zkmi_note_tree_free(zkmi_note_tree* tree);
+/* out = height, capacity, n_leaves */
+int32_t zkmi_note_tree_shape(const zkmi_note_tree* tree, uint64_t out[3]);
+int32_t zkmi_note_tree_root(zkmi_ctx* ctx, const zkmi_note_tree* tree, uint8_t out_root[32]);
+/* m leaves (32 B canonical LE each) appended at indices n .. n+m-1.  out_root (optional) = the new root; out_roots /
+ * d_roots (optional) = m x 32 B, roots[j] = the root of the tree holding leaves 0 .. n+j: what the contract's add_leaf
+ * logs per leaf (contract/merkle.rs:48-80).  roots[m-1] = out_root. */
+int32_t zkmi_note_tree_append(zkmi_ctx* ctx, zkmi_note_tree* tree, const uint8_t* leaves, uint64_t m, uint8_t out_root[32],
+                              uint8_t* out_roots);
+int32_t zkmi_note_tree_append_dev(zkmi_ctx* ctx, zkmi_note_tree* tree, const void* d_leaves, uint64_t m, uint8_t out_root[32],
+                                  void* d_roots);
+/* Paths of k leaves against the current root: k x height shape bytes, k x height x 32 B siblings, leaf level first
+ * (MerkleProof::{path_shape, path} of zkmi_note_update; the inputs of zkmi_poseidon_merkle_roots_dev).  leaf_idx is a
+ * host array in both; indices may repeat and come in any order.  k = 0 writes nothing. */
+int32_t zkmi_note_tree_paths(zkmi_ctx* ctx, const zkmi_note_tree* tree, const uint64_t* leaf_idx, uint32_t k, uint8_t* out_shape,
+                             uint8_t* out_paths);
+int32_t zkmi_note_tree_paths_dev(zkmi_ctx* ctx, const zkmi_note_tree* tree, const uint64_t* leaf_idx, uint32_t k, void* d_shape,
+                                 void* d_paths);
+
 /* ---- rows a1-a5 with real hashing: the update_note relation ---------------- *
  * update_note_circuit (shielder/relations/src/relations/update_note.rs:106-149) with
  * verify_note_circuit (:91-103), CircuitMerkleProof::verify (merkle_proof.rs:38-61)
@@ -398,6 +438,15 @@ int32_t zkmi_update_note_witness(uint32_t log_n, int32_t op_kind, const zkmi_not
  * _prove_batch_dev), out_status[i] = ZKMI_OK or the mock's error code for that instance. */
 int32_t zkmi_update_note_witness_batch_dev(zkmi_ctx* ctx, uint32_t log_n, int32_t op_kind, const zkmi_note_update* in,
                                            uint32_t n, void* const* d_z_out, int32_t* out_status);
+/* zkmi_update_note_witness_batch_dev with tree_height / path_shape / path of every in[i] ignored and taken on the
+ * device from the path of leaf_idx[i] (a host array) in `tree`, against its current root: no path travels through the
+ * host.  BLS12-381 Fr trees only (a BN254 tree, a tree of another context, a leaf_idx[i] >= n_leaves:
+ * ZKMI_ERR_BAD_ARG); the batch's height is the tree's.  The leaf at leaf_idx[i] is NOT compared with the instance's
+ * old-note hash: the relation computes the root, so a mismatch gives a satisfying assignment for another root.
+ * Statuses are those of zkmi_update_note_witness_batch_dev. */
+int32_t zkmi_update_note_witness_batch_tree_dev(zkmi_ctx* ctx, uint32_t log_n, int32_t op_kind, const zkmi_note_update* in,
+                                                const zkmi_note_tree* tree, const uint64_t* leaf_idx, uint32_t n,
+                                                void* const* d_z_out, int32_t* out_status);
 /* the same device code executed on the host for one instance (test hook: must equal
  * zkmi_update_note_witness byte for byte) */
 int32_t zkmi_update_note_witness_values_host(uint32_t log_n, int32_t op_kind, const zkmi_note_update* in, uint8_t* out_z);

@@ -26,6 +26,7 @@ pub const ZKMI_MAX_TREE_HEIGHT: usize = 32;
 #[repr(C)] pub struct zkmi_comm { _p: [u8; 0] }
 #[repr(C)] pub struct zkmi_vk { _p: [u8; 0] }
 #[repr(C)] pub struct zkmi_srs { _p: [u8; 0] }
+#[repr(C)] pub struct zkmi_note_tree { _p: [u8; 0] }
 
 /// = `Scalar { bytes: [u8; 32] }` (mocked_zk/src/scalar.rs:1-6), little-endian
 #[repr(C)] #[derive(Clone, Copy)] pub struct zkmi_scalar { pub bytes: [u8; 32] }
@@ -74,6 +75,23 @@ extern "C" {
     pub fn zkmi_update_note_witness(log_n: u32, op_kind: i32, input: *const zkmi_note_update, out_z: *mut u8, out_publics: *mut u8) -> i32;
     pub fn zkmi_update_note_witness_batch_dev(ctx: *mut zkmi_ctx, log_n: u32, op_kind: i32, input: *const zkmi_note_update, n: u32,
                                               d_z_out: *const *mut core::ffi::c_void, out_status: *mut i32) -> i32;
+    // the resident Poseidon note tree (field 0 = BLS12-381 Fr, 1 = BN254 Fr): appends of a block's notes, the root after each
+    // leaf (what add_leaf logs), paths against the current root, and the witness batch with its paths taken from the tree
+    pub fn zkmi_note_tree_create(ctx: *mut zkmi_ctx, field: i32, height: u32, capacity: u64, out: *mut *mut zkmi_note_tree) -> i32;
+    pub fn zkmi_note_tree_free(tree: *mut zkmi_note_tree) -> i32;
+    pub fn zkmi_note_tree_shape(tree: *const zkmi_note_tree, out: *mut u64) -> i32;
+    pub fn zkmi_note_tree_root(ctx: *mut zkmi_ctx, tree: *const zkmi_note_tree, out_root: *mut u8) -> i32;
+    pub fn zkmi_note_tree_append(ctx: *mut zkmi_ctx, tree: *mut zkmi_note_tree, leaves: *const u8, m: u64, out_root: *mut u8,
+                                 out_roots: *mut u8) -> i32;
+    pub fn zkmi_note_tree_append_dev(ctx: *mut zkmi_ctx, tree: *mut zkmi_note_tree, d_leaves: *const core::ffi::c_void, m: u64,
+                                     out_root: *mut u8, d_roots: *mut core::ffi::c_void) -> i32;
+    pub fn zkmi_note_tree_paths(ctx: *mut zkmi_ctx, tree: *const zkmi_note_tree, leaf_idx: *const u64, k: u32, out_shape: *mut u8,
+                                out_paths: *mut u8) -> i32;
+    pub fn zkmi_note_tree_paths_dev(ctx: *mut zkmi_ctx, tree: *const zkmi_note_tree, leaf_idx: *const u64, k: u32,
+                                    d_shape: *mut core::ffi::c_void, d_paths: *mut core::ffi::c_void) -> i32;
+    pub fn zkmi_update_note_witness_batch_tree_dev(ctx: *mut zkmi_ctx, log_n: u32, op_kind: i32, input: *const zkmi_note_update,
+                                                   tree: *const zkmi_note_tree, leaf_idx: *const u64, n: u32,
+                                                   d_z_out: *const *mut core::ffi::c_void, out_status: *mut i32) -> i32;
     pub fn zkmi_create_note_r1cs(log_n: u32, out: *mut *mut zkmi_r1cs) -> i32;
     pub fn zkmi_create_note_witness(log_n: u32, input: *const zkmi_note_create, out_z: *mut u8, out_publics: *mut u8) -> i32;
     pub fn zkmi_r1cs_shape(r: *const zkmi_r1cs, n_vars: *mut u32, n_pub: *mut u32, n_constraints: *mut u32, log_n: *mut u32) -> i32;

@@ -40,4 +40,5 @@ from .binding import (  # noqa: F401
     PK2_BAD_L,
     Srs,
     ProvingKey,
+    NoteTree,
 )

@@ -923,6 +923,67 @@ class Context:
         self._chk(self.lib.zkmi_update_note_witness_batch_dev(self.h, C.c_uint32(log_n), C.c_int32(op_kind), arr, C.c_uint32(n), ptrs, st))
         return list(st)[:n]
 
+    # ---- the resident Poseidon note tree (include/zkmi.h "note tree") ---------
+    def note_tree(self, height, capacity, field=0):
+        h = C.c_void_p()
+        self._chk(self.lib.zkmi_note_tree_create(self.h, C.c_int32(field), C.c_uint32(height), C.c_uint64(capacity), C.byref(h)))
+        return NoteTree(self, h, field)
+
+    def append(self, tree, leaves, want_roots=False):
+        """m = len(leaves) / 32 leaves (bytes) behind the tree's last one -> (new root, m x 32 B per-leaf roots or None)."""
+        assert len(leaves) % 32 == 0
+        m = len(leaves) // 32
+        root = (C.c_uint8 * 32)()
+        roots = (C.c_uint8 * (32 * max(1, m)))() if want_roots else None
+        self._chk(self.lib.zkmi_note_tree_append(self.h, tree.h, _buf(leaves), C.c_uint64(m), root, roots))
+        return bytes(root), (bytes(roots)[: 32 * m] if want_roots else None)
+
+    def append_dev(self, tree, d_leaves, m, d_roots=None):
+        """m leaves from the device buffer d_leaves; d_roots (optional device buffer, m x 32 B) receives the per-leaf roots."""
+        root = (C.c_uint8 * 32)()
+        self._chk(self.lib.zkmi_note_tree_append_dev(self.h, tree.h, C.c_void_p(d_leaves), C.c_uint64(m), root,
+                                                     C.c_void_p(d_roots) if d_roots else None))
+        return bytes(root)
+
+    def root(self, tree):
+        out = (C.c_uint8 * 32)()
+        self._chk(self.lib.zkmi_note_tree_root(self.h, tree.h, out))
+        return bytes(out)
+
+    def shape(self, tree):
+        """(height, capacity, n_leaves)"""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.lib.zkmi_note_tree_shape(tree.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def paths(self, tree, leaf_idx):
+        """(shape bytes k x height, path bytes k x height x 32) of the given leaves against the current root."""
+        k, height = len(leaf_idx), self.shape(tree)[0]
+        idx = (C.c_uint64 * max(1, k))(*leaf_idx)
+        shape = (C.c_uint8 * max(1, k * height))()
+        paths = (C.c_uint8 * max(1, 32 * k * height))()
+        self._chk(self.lib.zkmi_note_tree_paths(self.h, tree.h, idx, C.c_uint32(k), shape, paths))
+        return bytes(shape)[: k * height], bytes(paths)[: 32 * k * height]
+
+    def paths_dev(self, tree, leaf_idx, d_shape, d_paths):
+        """The same into device buffers (k x height bytes, k x height x 32 B)."""
+        k = len(leaf_idx)
+        idx = (C.c_uint64 * max(1, k))(*leaf_idx)
+        self._chk(self.lib.zkmi_note_tree_paths_dev(self.h, tree.h, idx, C.c_uint32(k), C.c_void_p(d_shape), C.c_void_p(d_paths)))
+
+    def update_note_witness_batch_tree_dev(self, log_n, op_kind, inputs, tree, leaf_idx, d_ptrs):
+        """update_note_witness_batch_dev with the Merkle inputs of inputs[i] taken on the device from the path of
+        leaf_idx[i] in `tree`; returns the per-instance status codes."""
+        n = len(inputs)
+        assert n == len(d_ptrs) == len(leaf_idx)
+        arr = (NoteUpdate * max(1, n))(*inputs)
+        idx = (C.c_uint64 * max(1, n))(*leaf_idx)
+        ptrs = (C.c_void_p * max(1, n))(*[int(p) for p in d_ptrs])
+        st = (C.c_int32 * max(1, n))()
+        self._chk(self.lib.zkmi_update_note_witness_batch_tree_dev(self.h, C.c_uint32(log_n), C.c_int32(op_kind), arr, tree.h, idx,
+                                                                   C.c_uint32(n), ptrs, st))
+        return list(st)[:n]
+
     # ---- BN254 MSM / NTT / KZG commit (SURVEY.md 8f-3) -----------------------
     def bn254_bases(self, affine, check=True):
         h = C.c_void_p()
@@ -1392,6 +1453,36 @@ class Srs:
     def free(self):
         if self.h:
             self.ctx.lib.zkmi_srs_free(self.h)
+            self.h = None
+
+
+class NoteTree:
+    """A resident append-only Poseidon note tree (zkmi_note_tree): batched appends, per-leaf roots and paths in HBM."""
+
+    def __init__(self, ctx, h, field):
+        self.ctx, self.h, self.field = ctx, h, field
+
+    def shape(self):
+        return self.ctx.shape(self)
+
+    def root(self):
+        return self.ctx.root(self)
+
+    def append(self, leaves, want_roots=False):
+        return self.ctx.append(self, leaves, want_roots)
+
+    def append_dev(self, d_leaves, m, d_roots=None):
+        return self.ctx.append_dev(self, d_leaves, m, d_roots)
+
+    def paths(self, leaf_idx):
+        return self.ctx.paths(self, leaf_idx)
+
+    def paths_dev(self, leaf_idx, d_shape, d_paths):
+        return self.ctx.paths_dev(self, leaf_idx, d_shape, d_paths)
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.zkmi_note_tree_free(self.h)
             self.h = None
 
 

@@ -19,12 +19,14 @@
 // 128-bit range = 129.  The relation proper has a few thousand constraints; the remainder up to
 // constraints + publics = 2^log_n is the multiplication chain SURVEY.md §8d prescribes
 // (s_{k+1} = s_k^2 + s_{k-1}, seeded from the loaded inputs).
+#include <stddef.h>
 #include <string.h>
 #include <algorithm>
 #include <mutex>
 #include <new>
 #include <utility>
 #include "ctx.hpp"
+#include "note_tree.hpp"
 #include "poseidon.hpp"
 #include "r1cs.hpp"
 #include "relation_values.hpp"
@@ -549,6 +551,25 @@ __global__ __launch_bounds__(64) void k_update_note_values(const zkmi_note_updat
   status[i] = rv_update_note(in[i], op_kind, height, K, n_free, c, z_out[i]);
 }
 
+// zkmi_update_note_witness_batch_tree_dev: thread (i, l), l < height, overwrites path_shape[l] and path[l] of the staged
+// instance i with the sibling of leaf idx[i] at level l of the note tree (note_tree.hpp; k_merkle_paths' shape convention),
+// thread (i, 0) also its tree_height.  Entries behind the height stay as sent: the relation ignores them.
+static_assert(offsetof(zkmi_note_update, path) % 4 == 0 && sizeof(zkmi_note_update) % 4 == 0, "path entries are written as words");
+__global__ __launch_bounds__(256) void k_note_paths_fill(zkmi_note_update* __restrict__ in, uint32_t n, NoteTreeView t,
+                                                         uint64_t n_leaves, const uint64_t* __restrict__ idx) {
+  const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (uint64_t)n * t.height) return;
+  const uint32_t i = (uint32_t)(q / t.height), level = (uint32_t)(q % t.height);
+  const uint64_t pos = idx[i] >> level;
+  const uint32_t* src = t.node_or_z(n_leaves, level, pos ^ 1);
+  zkmi_note_update& u = in[i];
+  u.path_shape[level] = (uint8_t)(1u - (uint32_t)(pos & 1));
+  uint32_t* dst = reinterpret_cast<uint32_t*>(u.path[level].bytes);
+#pragma unroll
+  for (int k = 0; k < 8; k++) dst[k] = src[k];
+  if (level == 0) u.tree_height = t.height;
+}
+
 }  // namespace
 }  // namespace zkmi
 
@@ -638,6 +659,53 @@ int32_t zkmi_update_note_witness_batch_dev(zkmi_ctx* ctx, uint32_t log_n, int32_
   ZK_HIP(ctx, hipMemcpyAsync(d, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   ZK_HIP(ctx, hipMemcpyAsync(d + off_ptr, d_z_out, ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (ctx->timer()) ctx->timer()->begin(PH_WITNESS, ctx->stream);
+  hipLaunchKernelGGL(k_update_note_values, dim3((n + 63) / 64), dim3(64), 0, ctx->stream,
+                     reinterpret_cast<const zkmi_note_update*>(d), n, op_kind, height, sh.K, sh.n_free,
+                     static_cast<const PoseidonConsts<Fr28>*>(ctx->d_pos[ZKMI_FIELD_BLS12_381_FR]),
+                     reinterpret_cast<uint32_t* const*>(d + off_ptr), reinterpret_cast<int32_t*>(d + off_st));
+  if (ctx->timer()) ctx->timer()->end(PH_WITNESS, ctx->stream);
+  ZK_HIP(ctx, hipGetLastError());
+  ZK_HIP(ctx, hipMemcpyAsync(out_status, d + off_st, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ZKMI_OK;
+}
+
+// The same batch with the Merkle inputs taken on the device from a resident note tree (note_tree.hip): tree_height,
+// path_shape and path of every in[i] are ignored and overwritten in the staged copy with the tree's height and the path
+// of leaf_idx[i] against the current root; then the same kernel runs.  The leaf is not compared with the instance's
+// old-note hash: the relation computes the root, so a mismatch gives a satisfying assignment for another root.
+int32_t zkmi_update_note_witness_batch_tree_dev(zkmi_ctx* ctx, uint32_t log_n, int32_t op_kind, const zkmi_note_update* in,
+                                                const zkmi_note_tree* tree, const uint64_t* leaf_idx, uint32_t n,
+                                                void* const* d_z_out, int32_t* out_status) {
+  ZK_ENTER(ctx);
+  if (log_n < 13 || log_n > 26 || (op_kind != ZKMI_OP_DEPOSIT && op_kind != ZKMI_OP_WITHDRAW) || !tree || tree->ctx != ctx ||
+      tree->device != ctx->device || tree->field != ZKMI_FIELD_BLS12_381_FR || (n && (!in || !leaf_idx || !d_z_out || !out_status)))
+    return ZKMI_ERR_BAD_ARG;
+  for (uint32_t i = 0; i < n; i++)
+    if (leaf_idx[i] >= tree->n) return ctx->fail(ZKMI_ERR_BAD_ARG, "leaf index behind the tree's leaves");
+  if (n == 0) return ZKMI_OK;
+  const int height = (int)tree->view.height;
+  ChainShape sh;
+  const int32_t rc = chain_shape(log_n, op_kind, height, &sh);
+  if (rc != ZKMI_OK) return rc;
+  if (!ctx->d_pos[ZKMI_FIELD_BLS12_381_FR]) {
+    ZK_HIP(ctx, hipMalloc(&ctx->d_pos[ZKMI_FIELD_BLS12_381_FR], sizeof(PoseidonConsts<Fr28>)));
+    ZK_HIP(ctx, hipMemcpy(ctx->d_pos[ZKMI_FIELD_BLS12_381_FR], poseidon_consts_bls(), sizeof(PoseidonConsts<Fr28>),
+                          hipMemcpyHostToDevice));
+  }
+  const size_t in_bytes = sizeof(zkmi_note_update) * (size_t)n, ptr_bytes = sizeof(void*) * (size_t)n;
+  const size_t off_ptr = (in_bytes + 255) & ~(size_t)255, off_st = (off_ptr + ptr_bytes + 255) & ~(size_t)255;
+  const size_t off_idx = (off_st + sizeof(int32_t) * (size_t)n + 255) & ~(size_t)255;
+  ZK_HIP(ctx, ctx->staging(off_idx + sizeof(uint64_t) * (size_t)n));
+  uint8_t* d = static_cast<uint8_t*>(ctx->d_tmp);
+  ZK_HIP(ctx, hipMemcpyAsync(d, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(ctx, hipMemcpyAsync(d + off_ptr, d_z_out, ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(ctx, hipMemcpyAsync(d + off_idx, leaf_idx, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (ctx->timer()) ctx->timer()->begin(PH_WITNESS, ctx->stream);
+  const uint64_t cells = (uint64_t)n * (uint64_t)height;
+  hipLaunchKernelGGL(k_note_paths_fill, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, ctx->stream,
+                     reinterpret_cast<zkmi_note_update*>(d), n, tree->view, tree->n, reinterpret_cast<const uint64_t*>(d + off_idx));
+  ZK_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_update_note_values, dim3((n + 63) / 64), dim3(64), 0, ctx->stream,
                      reinterpret_cast<const zkmi_note_update*>(d), n, op_kind, height, sh.K, sh.n_free,
                      static_cast<const PoseidonConsts<Fr28>*>(ctx->d_pos[ZKMI_FIELD_BLS12_381_FR]),
